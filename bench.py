@@ -15,10 +15,17 @@ logistic128 (config 3), hmc1024 (config 4, per-GPU shard), linear512
 unit (benchmarks/benchunits/binomial.jl: logistic n=1000, d=10, RWM(0.1), 100
 steps), printed beside its benchlog.csv numbers.
 
-  python bench.py [--config metric] [--gpus N --steps K --warmup W]
+  python bench.py [--config metric] [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU; weak scaling:
                                                       every rank runs the per-GPU chain count)
 Prints one JSON line (rank 0).
+
+A plain run sets up, warms up, times the `--steps` steps and prints the headline line (metric, value, unit,
+ms_per_step, the workload's configuration).  `--dump-outputs DIR` also writes what the timed run returned
+(kept samples, gradients, accept bits; a fixed sample of the chains when they exceed DUMP_BUDGET_BYTES) as
+DIR/<name>.npy.  `--full` adds everything else to the line, each after the timed region: the roofline object,
+the acceptance rate, the ESS/sec leg, the CPU baseline, the reference's benchmark units (binomial,
+bare_normal), `--pcie` and the multi-GPU gather.
 """
 from __future__ import annotations
 
@@ -101,13 +108,51 @@ def parse():
     p.add_argument("--thinning", type=int, default=None)
     p.add_argument("--spl", type=int, default=-1, help="steps per launch (0: whole run in one launch; "
                                                        "-1: default of the library)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-ess", action="store_true", help="skip the ESS/sec leg")
+    p.add_argument("--full", action="store_true", help="after the timed run, also the roofline object, acceptance, "
+                                                       "ESS/sec, the CPU baseline, the reference's benchmark "
+                                                       "units, --pcie and the multi-GPU gather")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the timed run's outputs (kept samples, gradients, accept bits) as DIR/<name>.npy")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-ess", action="store_true", help="with --full: skip the ESS/sec leg")
     p.add_argument("--cpu-seconds", type=float, default=12.0)
     p.add_argument("--strong", action="store_true", help="fixed total chains (--chains) split over ranks")
-    p.add_argument("--pcie", action="store_true", help="also time one run with host output buffers (kept samples "
-                                                       "cross PCIe after the loop); reported apart, never `value`")
-    return p.parse_args()
+    p.add_argument("--pcie", action="store_true", help="with --full: also time one run with host output buffers (kept "
+                                                       "samples cross PCIe after the loop); reported apart, never "
+                                                       "`value`")
+    args = p.parse_args()
+    if args.pcie and not args.full:
+        p.error("--pcie is a --full leg")
+    return args
+
+
+DUMP_BUDGET_BYTES = 48 << 20      # --dump-outputs: all files of one rank together stay under this
+DUMP_SAMPLE_SEED = 0xD0
+
+
+def dump_outputs(path, rank, samples, grads, bits, C):
+    """--dump-outputs: what the timed run handed its caller -- samples [kept][d][C], gradients (gradient samplers)
+    and the accept bits, unpacked to 0/1 as accept [kept][C] -- as path/<name>.npy (rank 0; other ranks append
+    _rank<r>), float64 and float32.  When the arrays exceed DUMP_BUDGET_BYTES, a fixed sample of the chains is
+    written: the same sorted chain indices (numpy Philox, DUMP_SAMPLE_SEED) for every array and every run of the
+    same arguments."""
+    import torch
+    nkept, d = samples.shape[0], samples.shape[1]
+    per_chain = max(1, nkept * (8 * d * (2 if grads is not None else 1) + 4))
+    n = min(C, max(1, DUMP_BUDGET_BYTES // per_chain))
+    if n < C:
+        g = np.random.Generator(np.random.Philox(key=DUMP_SAMPLE_SEED))
+        idx = np.sort(g.choice(C, size=n, replace=False))
+    else:
+        idx = np.arange(C)
+    ti = torch.from_numpy(idx).to(samples.device)
+    arrays = {"samples": samples.index_select(2, ti)}
+    if grads is not None:
+        arrays["gradients"] = grads.index_select(2, ti)
+    arrays["accept"] = ((bits.index_select(1, ti // 64) >> (ti % 64)) & 1).to(torch.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ("" if rank == 0 else f"_rank{rank}") + ".npy"), a.cpu().numpy())
 
 
 def regression_data(kind, n, d, key=0x5EED):
@@ -551,6 +596,47 @@ def main():
         T, kernel_ms = float(t[0]), float(t[1])
     total_chains = C * world
     value = total_chains * K / T
+    spl = args.spl if args.spl >= 0 else 0
+    # per-GPU workload key: the PMC traffic of a committed rocprofv3 run of this same workload
+    # (profiles/traffic.json, written by scripts/summarize_prof.py) fills roofline.traffic
+    wkey = f"{args.config}|d={d}|chains={C}|{args.sampler}|steps={K}|thinning={args.thinning}|spl={spl}"
+    line = {
+        "metric": "MCMC steps*chains/sec (1M chains, d=32)" if args.config == "metric"
+        else f"MCMC steps*chains/sec ({cfg0['desc'].split(':')[0]})",
+        "value": value,
+        "unit": "chain-steps/s",
+        "n_gpus": world,
+        "steps": K,
+        "warmup": W,
+        "ms_per_step": T * 1e3 / K,
+        "higher_is_better": True,
+        "scaling": "strong" if args.strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic (chains start at model.init; Philox4x32-10 streams, seed 1"
+                + ("; regression data from numpy Philox, key 0x5EED)" if cfg0["model"] not in ("iso", "distobs")
+                   else ")"),
+        "config": {
+            "workload": f"{args.config}: {cfg0['desc']}; SerialMC(steps={K}, burnin={burnin}, "
+                        f"thinning={args.thinning}), {C} chains/GPU, {type(sampler).__name__}",
+            "d": d, "chains_per_gpu": C, "global_chains": total_chains, "sampler": args.sampler,
+            "burnin": burnin, "thinning": args.thinning, "kept_per_chain": nkept,
+            "steps_per_launch": spl, "evals": evals, "key": wkey,
+            "parallelism": f"chains sharded over {world} GPU(s), no collective in the step loop",
+            "process_group": (("nccl (RCCL)" if backend == "nccl" else backend) if dist is not None else None),
+        },
+    }
+    if adapt is not None:
+        line["adaptation"] = adapt
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, samples, grads, bits, C)
+    if not args.full:                                   # a plain run: the headline line and nothing after it
+        if rank == 0:
+            print(json.dumps(line), file=json_out, flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ESS/sec: sum over chains of min over parameters of the IMSE ESS of the kept
     # samples, per second of sampling; computed on the device after the timed region, timed apart.  When the
@@ -671,13 +757,9 @@ def main():
                           "landed chunk copied to page-locked host memory on a side stream while the next arrives; "
                           "timed apart (max over ranks); never inside the step loop"}
         del g_out, gparts
-    spl = args.spl if args.spl >= 0 else 0
     nl = ct.c_int64(0)
     _lib.check(lib.mcmc_chains_launches(h, K, ct.byref(nl)))
     launches = nl.value                                  # the library's plan (some kernels fuse one step)
-    # per-GPU workload key: the PMC traffic of a committed rocprofv3 run of this same workload
-    # (profiles/traffic.json, written by scripts/summarize_prof.py) fills roofline.traffic
-    wkey = f"{args.config}|d={d}|chains={C}|{args.sampler}|steps={K}|thinning={args.thinning}|spl={spl}"
     kname = task.step_kernel                            # the instance the timed run launched (C ABI)
     tdet = measured_traffic(wkey, kname)
     traffic = tdet["bytes_per_launch"] if tdet else None
@@ -811,37 +893,7 @@ def main():
         roof["leapfrogs_per_chain_step" if args.sampler in ("hmc", "hmcda") else "evals_per_chain_step"] = \
             evals / (C * K)
         roof["chain_evals_per_s"] = evals * world / T
-    line = {
-        "metric": "MCMC steps*chains/sec (1M chains, d=32)" if args.config == "metric"
-        else f"MCMC steps*chains/sec ({cfg0['desc'].split(':')[0]})",
-        "value": value,
-        "unit": "chain-steps/s",
-        "n_gpus": world,
-        "steps": K,
-        "warmup": W,
-        "ms_per_step": T * 1e3 / K,
-        "higher_is_better": True,
-        "scaling": "strong" if args.strong else "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic (chains start at model.init; Philox4x32-10 streams, seed 1"
-                + ("; regression data from numpy Philox, key 0x5EED)" if cfg0["model"] not in ("iso", "distobs")
-                   else ")"),
-        "config": {
-            "workload": f"{args.config}: {cfg0['desc']}; SerialMC(steps={K}, burnin={burnin}, "
-                        f"thinning={args.thinning}), {C} chains/GPU, {type(sampler).__name__}",
-            "d": d, "chains_per_gpu": C, "global_chains": total_chains, "sampler": args.sampler,
-            "burnin": burnin, "thinning": args.thinning, "kept_per_chain": nkept,
-            "steps_per_launch": spl, "evals": evals, "key": wkey,
-            "parallelism": f"chains sharded over {world} GPU(s), no collective in the step loop",
-            "process_group": (("nccl (RCCL)" if backend == "nccl" else backend) if dist is not None else None),
-        },
-        "roofline": roof,
-        "acceptance": acceptance,
-        "ess": ess_line,
-    }
-    if adapt is not None:
-        line["adaptation"] = adapt
+    line.update({"roofline": roof, "acceptance": acceptance, "ess": ess_line})
     if args.config in ("binomial", "bare_normal") and rank == 0:
         line["reference_units"] = binomial_units(mc, model, C, local, args.config)
     if pcie is not None:

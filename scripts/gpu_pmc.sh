@@ -11,7 +11,7 @@ PGROUPS=${PMC_GROUPS:-"SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INS
 IFS=';' read -ra GRPS <<< "$PGROUPS"
 for grp in "${GRPS[@]}"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --pmc $grp --output-format csv -d "$O/p$i" -o run -- python3 bench.py --no-cpu-baseline "$@" > "$O/p$i.log" 2>&1
+  timeout -k 10 300 rocprofv3 --pmc $grp --output-format csv -d "$O/p$i" -o run -- python3 bench.py --full --no-cpu-baseline "$@" > "$O/p$i.log" 2>&1
   rc=$?
   echo "pass $i rc $rc" | tee -a "$O/steps.txt"
   case $rc in 0|1) ;; *) echo "stopping (rc $rc)"; exit $rc;; esac

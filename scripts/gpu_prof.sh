@@ -12,7 +12,7 @@ run() {  # run <name> <timeout> <cmd...>
   echo "$name exit $rc" | tee -a "$O/steps.txt"
   [ $rc -eq 0 ] || { echo "stopping after $name (rc $rc)"; exit $rc; }
 }
-run trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -o run -- python3 bench.py --no-cpu-baseline "$@"
-run fetch 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/fetch" -o run -- python3 bench.py --no-cpu-baseline "$@"
-run write 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$O/write" -o run -- python3 bench.py --no-cpu-baseline "$@"
+run trace 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -o run -- python3 bench.py --full --no-cpu-baseline "$@"
+run fetch 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$O/fetch" -o run -- python3 bench.py --full --no-cpu-baseline "$@"
+run write 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$O/write" -o run -- python3 bench.py --full --no-cpu-baseline "$@"
 echo prof-done

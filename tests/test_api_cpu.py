@@ -232,6 +232,69 @@ def test_bench_valu_roofline_profile():
         assert 0.3 < frac_at_clock <= 1.0 + 1e-6, (k, frac_at_clock)
 
 
+@pytest.mark.parametrize("nkept,d,C,with_grads,budget", [(3, 5, 130, True, None), (2, 4, 1000, False, 20000),
+                                                         (3, 5, 1000, True, 20000), (0, 4, 70, False, None)])
+def test_bench_dump_outputs(tmp_path, monkeypatch, nkept, d, C, with_grads, budget):
+    """bench.py --dump-outputs writes float arrays of the timed run's outputs: every chain when they fit
+    DUMP_BUDGET_BYTES, else the same sorted Philox sample of chains in every array and every run; the accept
+    bits come out unpacked (bit c % 64 of word c // 64, as api._unpack_bits)."""
+    import importlib
+    import torch
+    bench = importlib.import_module("bench")
+    assert bench.DUMP_BUDGET_BYTES <= 64e6
+    if budget is not None:
+        monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", budget)
+    rng = np.random.default_rng(3)
+    s = rng.standard_normal((nkept, d, C))
+    g = rng.standard_normal((nkept, d, C)) if with_grads else None
+    acc = rng.random((nkept, C)) < 0.5
+    words = np.zeros((nkept, (C + 63) // 64), dtype=np.uint64)
+    for k in range(nkept):
+        on = np.nonzero(acc[k])[0]
+        np.bitwise_or.at(words[k], on // 64, np.uint64(1) << (on % 64).astype(np.uint64))
+    t = lambda a: None if a is None else torch.from_numpy(a)
+    out = []
+    for rep in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / rep), 0, t(s), t(g), t(words.view(np.int64)), C)
+        out.append({f: np.load(tmp_path / rep / f) for f in sorted(os.listdir(tmp_path / rep))})
+    a, b = out
+    assert sorted(a) == sorted(["accept.npy", "samples.npy"] + (["gradients.npy"] if with_grads else []))
+    assert all(np.array_equal(a[f], b[f]) for f in a)
+    assert a["samples.npy"].dtype == np.float64 and a["accept.npy"].dtype == np.float32
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BUDGET_BYTES
+    n = a["samples.npy"].shape[2]
+    if nkept * (8 * d * (2 if with_grads else 1) + 4) * C <= bench.DUMP_BUDGET_BYTES:
+        assert n == C
+        idx = np.arange(C)
+    else:
+        assert 0 < n < C
+        idx = np.sort(np.random.Generator(np.random.Philox(key=bench.DUMP_SAMPLE_SEED)).choice(C, n, replace=False))
+    assert np.array_equal(a["samples.npy"], s[:, :, idx])
+    assert np.array_equal(a["accept.npy"], acc[:, idx].astype(np.float32))
+    if with_grads:
+        assert np.array_equal(a["gradients.npy"], g[:, :, idx])
+
+
+def test_bench_plain_run_and_full_options():
+    """--full and --dump-outputs exist, both off by default; --pcie is one of --full's legs."""
+    import importlib
+    import sys
+    bench = importlib.import_module("bench")
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"]
+        a = bench.parse()
+        assert a.full is False and a.dump_outputs is None and a.steps == 20 and a.warmup == 5
+        sys.argv += ["--full", "--pcie", "--dump-outputs", "x"]
+        a = bench.parse()
+        assert a.full and a.pcie and a.dump_outputs == "x"
+        sys.argv = ["bench.py", "--pcie"]
+        with pytest.raises(SystemExit):
+            bench.parse()
+    finally:
+        sys.argv = argv
+
+
 def _c_struct_fields(name):
     """(field, julia type) of a typedef struct in include/mcmc_hip.h, in order."""
     import re
