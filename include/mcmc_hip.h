@@ -11,7 +11,7 @@
  *   -----------------------------------------------  -------------------------------------------
  *   model(f; init, grad, scale)      mcmcmodels.jl:27-33,   mcmc_model_create (catalogue kind, init,
  *     MCMCLikelihoodModel ctor        likmodel.jl:100-143    scale, data X/Y)
- *   RWM / MALA / HMC / HMCDA ctors   RWM.jl:24-36,          mcmc_sampler_cfg (validated like the
+ *   RWM / MALA / HMC / HMCDA / NUTS  RWM.jl:24-36,          mcmc_sampler_cfg (validated like the
  *                                    MALA.jl:50-62,         reference @asserts: mcmc_sampler_validate)
  *                                    HMC.jl:53-74,
  *                                    HMCDA.jl:24-43
@@ -94,7 +94,7 @@ enum {
 };
 
 /* samplers */
-enum { MCMC_RWM = 1, MCMC_MALA = 2, MCMC_HMC = 3, MCMC_HMCDA = 4, MCMC_RAM = 5 };
+enum { MCMC_RWM = 1, MCMC_MALA = 2, MCMC_HMC = 3, MCMC_HMCDA = 4, MCMC_RAM = 5, MCMC_NUTS = 6 };
 
 typedef struct mcmc_ctx mcmc_ctx;
 typedef struct mcmc_model mcmc_model;
@@ -118,10 +118,10 @@ typedef struct {
 } mcmc_model_desc;
 
 typedef struct {
-    int32_t kind;            /* MCMC_RWM | MCMC_MALA | MCMC_HMC | MCMC_HMCDA | MCMC_RAM           */
+    int32_t kind;            /* MCMC_RWM | MCMC_MALA | MCMC_HMC | MCMC_HMCDA | MCMC_RAM | MCMC_NUTS */
     double scale;            /* RWM, RAM: scale (RWM.jl:25, RAM.jl:23)                             */
     double drift_step;       /* MALA: driftStep (MALA.jl:51)                                       */
-    int64_t n_leaps;         /* HMC: nLeaps (HMC.jl:54)                                            */
+    int64_t n_leaps;         /* HMC: nLeaps (HMC.jl:54); NUTS: maxdoublings (NUTS.jl:31)          */
     double leap_step;        /* HMC: leapStep (HMC.jl:55)                                          */
     double rate, len, shrinkage, t0, step;   /* HMCDA (HMCDA.jl:25-29); rate: RAM target rate (RAM.jl:24) */
     int32_t tuner;           /* 0: nothing; 1: EmpiricalMCMCTuner (MALA, HMC)                      */
@@ -183,7 +183,12 @@ int mcmc_runner_validate(const mcmc_runner_cfg* cfg);
  * depend on the number of GPUs.  init_x: optional per-chain start [d][nchains]
  * (NULL -> every chain starts at model.init, RWM.jl:53).  Sizes built: d <= 16384 for the separable
  * models, d <= 1024 for the regression models; RAM d <= 1024 (separable and regression), else
- * MCMC_E_UNSUPPORTED. */
+ * MCMC_E_UNSUPPORTED.  NUTS (NUTS.jl:53-183): built for the separable targets with d <= 32 and the joint targets
+ * (DIST_OBS, OU; d <= 16), maxdoublings 1..10 (n_leaps; the reference default is 5).  Wider targets, the regression
+ * models and maxdoublings 11..19 (valid in the reference) answer MCMC_E_UNSUPPORTED; mcmc_run_seqmc refuses NUTS
+ * targets (NUTS adapts by its own step counter).  The initial epsilon search (NUTS.jl:71-82) runs here and again at
+ * mcmc_chains_reset; mcmc_chains_set_state keeps epsilon and the dual-averaging state (the :reset hook,
+ * NUTS.jl:61-63).  The accept bit of a kept NUTS step is 1 if any doubling's candidate was taken. */
 int mcmc_chains_create(mcmc_model* model, const mcmc_sampler_cfg* sampler, int64_t nchains,
                        int64_t chain_offset, uint64_t seed, const double* init_x, mcmc_chains** out);
 int mcmc_chains_destroy(mcmc_chains* chains);
@@ -204,11 +209,13 @@ int mcmc_chains_steps_done(mcmc_chains* chains, int64_t* steps);
 /* per-chain adaptive state after the last run, [nchains] each (any may be NULL): step = the current step size
  * (MALA driftStep under EmpiricalMALATune, HMC leapStep under EmpiricalHMCTune, HMCDA leapStep, HMCDA.jl:136,140);
  * step_bar = HMCDA's dual-averaged dualLeapStep (HMCDA.jl:138); nleaps = the tuned HMC nLeaps (HMC.jl:42).
+ * NUTS: step = epsilon, step_bar = exp(log epsilon_bar) (NUTS.jl:169-172).
  * A quantity the sampler does not adapt reads NaN (steps) or 0 (nleaps). */
 int mcmc_chains_tuner_state(mcmc_chains* chains, double* step, double* step_bar, int32_t* nleaps);
 /* log-target evaluations (with gradient for MALA/HMC/HMCDA) summed over all chains since
  * create/reset: steps x C for RWM/MALA, the leapfrog count for HMC/HMCDA (HMC.jl:93-102),
- * whose trajectory length varies per chain under HMCDA / EmpMCTuner. */
+ * whose trajectory length varies per chain under HMCDA / EmpMCTuner; NUTS: the leapfrogs of every tree and of
+ * the initial epsilon search. */
 int mcmc_chains_evals(mcmc_chains* chains, int64_t* evals);
 /* RAM: the current jump factor S of every chain (RAM.jl:55, :78), lower triangle packed by rows:
  * element (r, c), c <= r, of chain k at S[(r(r+1)/2 + c) * nchains + k]; host buffer of
@@ -245,6 +252,12 @@ int mcmc_chains_step_kernel(mcmc_chains* chains, char* buf, int64_t cap);
  * That run takes one step per launch.  pars == NULL switches it off; one run consumes the registration. */
 int mcmc_chains_store_leaps(mcmc_chains* chains, int64_t cap, double* pars, double* grads, double* mom, double* lp,
                             double* H, int32_t* nleaps);
+
+/* NUTS diagnostics (NUTS.jl:177; NUTS only, MCMC_E_INVALID_ARG otherwise).  The next mcmc_run_serialmc records, for
+ * every kept step, diagnostics["epsilon"] (the value after the step's adaptation) and diagnostics["ndoublings"] into
+ * epsilon, ndoublings [nkept][nchains] (on_device != 0: device pointers on the context's GPU).  epsilon == NULL
+ * switches it off; one run consumes the registration.  Group runs sample with NUTS but do not gather these two. */
+int mcmc_chains_nuts_diagnostics(mcmc_chains* chains, double* epsilon, int32_t* ndoublings, int32_t on_device);
 
 /* run_serialmc: consume runner->len steps, keep (burnin+1):thinning:len. */
 int mcmc_run_serialmc(mcmc_chains* chains, const mcmc_runner_cfg* runner, mcmc_outputs* out);

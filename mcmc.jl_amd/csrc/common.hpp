@@ -13,7 +13,7 @@ enum DistKind : int32_t {
     DK_NORMAL = 1, DK_UNIFORM = 2, DK_WEIBULL = 3, DK_BETA = 4, DK_TDIST = 5, DK_EXPONENTIAL = 6, DK_GAMMA = 7,
     DK_CAUCHY = 8, DK_LOGNORMAL = 9, DK_LAPLACE = 10
 };
-enum SamplerKind : int32_t { SK_RWM = 1, SK_MALA = 2, SK_HMC = 3, SK_HMCDA = 4, SK_RAM = 5 };
+enum SamplerKind : int32_t { SK_RWM = 1, SK_MALA = 2, SK_HMC = 3, SK_HMCDA = 4, SK_RAM = 5, SK_NUTS = 6 };
 
 // Model parameters as the kernels see them (device pointers).
 struct ModelArgs {
@@ -38,7 +38,7 @@ struct SamplerArgs {
     int32_t tuner;              // EmpMCTuner on/off
     double scale;               // RWM
     double drift_step;          // MALA
-    int64_t n_leaps;            // HMC
+    int64_t n_leaps;            // HMC; NUTS: maxdoublings
     double leap_step;           // HMC
     double rate, len, shrinkage, t0, step;  // HMCDA
     int64_t adapt_step, max_step;
@@ -51,9 +51,10 @@ struct ChainState {
     double* x;                  // [d][ld]  (lane-per-chain layout)   or [C][d] (wave-per-chain layout)
     double* lp;                 // [ld]
     double* g;                  // [d][ld] gradient at x (regression models only; separable models recompute)
-    double* t_step;             // MALA driftStep | HMC leapStep | HMCDA leapStep
-    double* t_bar;              // HMCDA dualLeapStep
-    double* t_h;                // HMCDA dualH
+    double* t_step;             // MALA driftStep | HMC leapStep | HMCDA leapStep | NUTS epsilon
+    double* t_bar;              // HMCDA dualLeapStep | NUTS log epsilon_bar (lebar)
+    double* t_h;                // HMCDA dualH | NUTS hbar
+    double* t_mu;               // NUTS mu = log(10 epsilon_0) (NUTS.jl:128)
     int32_t* t_leaps;           // HMC tuned nLeaps
     int32_t* t_acc;             // tuner accepted counter
     int32_t* t_prop;            // tuner proposed counter
@@ -63,6 +64,8 @@ struct ChainState {
     int64_t ram_ld;             // RAM: lane-per-chain: chain stride of ram_L (a multiple of 256); wave-per-chain:
                                 //      doubles per chain (ram.hpp wave layout)
     int64_t ram_hs;             // RAM: doubles from the first half of ram_L to the second
+    double* nuts_wv;            // NUTS level stack, vectors [maxdoublings][3][d][ld] (nuts.hpp; dead between steps)
+    double* nuts_ws;            // NUTS level stack, scalars [maxdoublings][4][ld] (two-lanes-per-chain: [2 ld])
 };
 
 // One launch of the fused step kernel.
@@ -86,6 +89,8 @@ struct StepArgs {
     int64_t nw;                 // words per kept step = ceil(C/64)
     int32_t* err;               // device error word
     unsigned long long* n_evals;  // running count of log-target evaluations over all chains (NULL: off)
+    double* nuts_eps;           // NUTS diagnostics["epsilon"] of the kept steps [nkept][C] (NULL: not stored)
+    int32_t* nuts_nd;           // NUTS diagnostics["ndoublings"] [nkept][C]
     const int32_t* order;       // regression HMC / HMCDA: chain slot -> local chain (NULL: identity), so that a
                                 // 16-chain MFMA tile holds chains of similar trajectory length
 };

@@ -25,6 +25,12 @@ hipError_t mcmc_launch_lpc_step(const mcmc::KernelArgs& a, hipStream_t st);
 hipError_t mcmc_launch_lpc_eval(const mcmc::KernelArgs& a, const double* xin, double* lp, double* g, int check,
                                 hipStream_t st);
 int mcmc_lpc_max_d();
+// NUTS (nuts.hip), lane-per-chain state, d <= mcmc_nuts_max_d(): the step loop (init == 0), or the initial epsilon
+// search after the chains' first evaluation (init != 0); the level stack lives in ChainState::nuts_wv / nuts_ws,
+// sized for SamplerArgs::n_leaps (maxdoublings <= mcmc_nuts_max_doublings()) levels
+hipError_t mcmc_launch_nuts(const mcmc::KernelArgs& a, int init, hipStream_t st);
+int mcmc_nuts_max_d();
+int mcmc_nuts_max_doublings();
 // wave-per-chain kernels (32 < d <= 4096), state [C][ld] (ld = row stride, multiple of 4)
 hipError_t mcmc_launch_wpc_step(const mcmc::KernelArgs& a, hipStream_t st);
 hipError_t mcmc_launch_wpc_eval(const mcmc::KernelArgs& a, const double* xin, double* lp, double* g, int check,

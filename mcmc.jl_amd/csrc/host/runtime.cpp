@@ -127,6 +127,11 @@ struct mcmc_chains {
     double *h_lpars = nullptr, *h_lgrads = nullptr, *h_lmom = nullptr, *h_llp = nullptr, *h_lH = nullptr;
     int32_t* h_lnl = nullptr;
     DevBuf leap_buf;
+    // NUTS diagnostics (mcmc_chains_nuts_diagnostics): buffers the next run fills (nuts_eps == NULL: off)
+    double* nuts_eps = nullptr;
+    int32_t* nuts_nd = nullptr;
+    bool nuts_on_device = false;
+    DevBuf nuts_buf;
     std::string step_kernel;         // the step kernel instance the last run launched
 };
 
@@ -279,6 +284,16 @@ extern "C" int mcmc_sampler_validate(const mcmc_sampler_cfg* s) {
             if (s->tuner) return fail(MCMC_E_UNSUPPORTED, "HMCDA takes no tuner");
             break;
         }
+        case MCMC_NUTS:
+            // n_leaps carries maxdoublings
+            if (!(s->n_leaps > 0)) return fail(MCMC_E_INVALID_ARG, "max doublings should be > 0");            // NUTS.jl:35
+            if (!(s->n_leaps < 20)) return fail(MCMC_E_INVALID_ARG, "max doublings reasonably be < 20");      // NUTS.jl:36
+            if (s->n_leaps > mcmc_nuts_max_doublings())
+                return fail(MCMC_E_UNSUPPORTED, "NUTS is built for maxdoublings <= " +
+                                                    std::to_string(mcmc_nuts_max_doublings()) +
+                                                    " (1 023 leapfrogs a step; the reference accepts up to 19)");
+            if (s->tuner) return fail(MCMC_E_UNSUPPORTED, "NUTS takes no tuner (NUTSTuner is abstract in the reference)");
+            break;
         default:
             return fail(MCMC_E_UNSUPPORTED, "unknown sampler kind");
     }
@@ -623,6 +638,7 @@ static void free_state(mcmc_chains* c) {
     ChainState& s = c->st;
     dfree(s.x); dfree(s.lp); dfree(s.g); dfree(s.t_step); dfree(s.t_bar); dfree(s.t_h);
     dfree(s.t_leaps); dfree(s.t_acc); dfree(s.t_prop); dfree(s.ram_L); dfree(s.mom);
+    dfree(s.t_mu); dfree(s.nuts_wv); dfree(s.nuts_ws);
     s = ChainState{};
 }
 
@@ -633,7 +649,20 @@ static hipError_t launch_chain_step(const mcmc_chains* c, const KernelArgs& a, h
         return mcmc_launch_glm_ram_wave(a, c->ram_u, c->ram_nz, c->xprop, c->lpp, st,
                                         st == ctx->stream ? ctx->stream2 : nullptr, ctx->ev_fork, ctx->ev_join);
     }
+    if (c->sa.kind == SK_NUTS) return mcmc_launch_nuts(a, 0, st);
     return launch_step(c->layout, a, st);
+}
+
+// the launch arguments that name a batch's chains and their random streams
+static void stream_args(const mcmc_chains* c, KernelArgs& a) {
+    a.sa = c->sa;
+    a.st = c->st;
+    a.s.chain0 = (uint32_t)c->offset;
+    a.s.key0 = (uint32_t)c->seed;
+    a.s.key1 = (uint32_t)(c->seed >> 32);
+    a.s.scale = c->d_scale_eff;
+    a.s.scale1 = c->scale1;
+    a.s.scale_uniform = c->scale_uniform;
 }
 
 // RWM, MALA and RAM evaluate the log-target once per chain-step, so a launch of n steps adds C n evaluations:
@@ -725,6 +754,13 @@ static int init_state(mcmc_chains* c) {
         HIP_TRY(mcmc_fill_f64(c->st.t_bar, c->C, 1.0, st));     // dualLeapStep = 1.
         HIP_TRY(mcmc_fill_f64(c->st.t_h, c->C, 0.0, st));       // dualH = 0.
     }
+    if (sa.kind == SK_NUTS) {
+        // the initial epsilon search and mu, hbar, lebar (NUTS.jl:71-82, 127-129), from the evaluated start; its
+        // leapfrogs are counted (d_evals was zeroed above)
+        stream_args(c, a);
+        a.s.n_evals = c->d_evals;
+        HIP_TRY(mcmc_launch_nuts(a, 1, st));
+    }
     if (sa.kind == SK_RAM) {
         // S = diag(model.scale .* sampler.scale) (RAM.jl:51,55) in half 0: packed rows in 64-chain tiles
         // (ram.hpp), diagonal (r, r) at row r(r+1)/2 + r of every tile; the padding block d..dpad-1 is the identity
@@ -765,7 +801,7 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
         return fail(MCMC_E_UNSUPPORTED, "RAM is built for d <= " + std::to_string(mcmc_wpc_ram_max_d()) +
                                         " (the d x d jump factor of every chain is kept in HBM)");
     if (s->kind != MCMC_RWM && s->kind != MCMC_RAM && !m->has_gradient) {
-        const char* nm = s->kind == MCMC_MALA ? "MALA" : s->kind == MCMC_HMC ? "HMC" : "HMCDA";
+        const char* nm = s->kind == MCMC_MALA ? "MALA" : s->kind == MCMC_HMC ? "HMC" : s->kind == MCMC_NUTS ? "NUTS" : "HMCDA";
         return fail(MCMC_E_NEEDS_GRADIENT, std::string(nm) + " sampler requires model with gradient function");
     }
     mcmc_ctx* ctx = m->ctx;
@@ -773,6 +809,15 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
     const int d = m->args.d;
     if (model_is_separable(m) && d > mcmc_wpc_max_d())
         return fail(MCMC_E_UNSUPPORTED, "separable targets support d <= 16384");
+    if (s->kind == MCMC_NUTS) {
+        if (model_is_glm(m))
+            return fail(MCMC_E_UNSUPPORTED, "NUTS is not built for the regression models (built: the separable and joint "
+                                            "targets with d <= " + std::to_string(mcmc_nuts_max_d()) + ")");
+        if (d > mcmc_nuts_max_d())
+            return fail(MCMC_E_UNSUPPORTED, "NUTS is built for d <= " + std::to_string(mcmc_nuts_max_d()) +
+                                                " (lane-per-chain and two-lanes-per-chain targets); d = " +
+                                                std::to_string(d));
+    }
     auto* c = new mcmc_chains();
     c->model = m;
     m->chains_alive += 1;
@@ -812,9 +857,17 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
         if (int r = dmalloc(&c->st.mom, (size_t)mcmc_glm_d_pad(d) * c->ld)) return bail(r);      // parking (glm_hmc)
     if (int r = dmalloc(&c->st.lp, nc)) return bail(r);
     const bool tuned = sa.tuner && (sa.kind == SK_MALA || sa.kind == SK_HMC);
-    if (tuned || sa.kind == SK_HMCDA)
+    if (tuned || sa.kind == SK_HMCDA || sa.kind == SK_NUTS)
         if (int r = dmalloc(&c->st.t_step, nc)) return bail(r);
-    if (sa.kind == SK_HMCDA) {
+    if (sa.kind == SK_NUTS) {
+        // mu, and the level stack of the tree walk (nuts.hpp): per level 3 vectors [d][ld] and 4 scalars per lane
+        // (two lanes per chain for d > 16), maxdoublings levels; dead between steps, so never copied
+        if (int r = dmalloc(&c->st.t_mu, nc)) return bail(r);
+        const size_t levels = (size_t)sa.n_leaps;
+        if (int r = dmalloc(&c->st.nuts_wv, levels * 3 * (size_t)d * (size_t)c->ld)) return bail(r);
+        if (int r = dmalloc(&c->st.nuts_ws, levels * 4 * (size_t)(d > 16 ? 2 : 1) * (size_t)c->ld)) return bail(r);
+    }
+    if (sa.kind == SK_HMCDA || sa.kind == SK_NUTS) {
         if (int r = dmalloc(&c->st.t_bar, nc)) return bail(r);
         if (int r = dmalloc(&c->st.t_h, nc)) return bail(r);
     }
@@ -881,6 +934,8 @@ extern "C" int mcmc_chains_destroy(mcmc_chains* c) {
     dfree(c->d_evals);
     dfree(c->out_samples.p);
     dfree(c->order_buf.p);
+    dfree(c->nuts_buf.p);
+    dfree(c->leap_buf.p);
     dfree(c->out_grads.p);
     dfree(c->out_bits.p);
     dfree(c->out_tmp.p);
@@ -982,6 +1037,7 @@ extern "C" int mcmc_chains_fork(mcmc_chains* src, int64_t first, int64_t count, 
     if (e == hipSuccess) e = vec(c->st.t_step, src->st.t_step, 8);
     if (e == hipSuccess) e = vec(c->st.t_bar, src->st.t_bar, 8);
     if (e == hipSuccess) e = vec(c->st.t_h, src->st.t_h, 8);
+    if (e == hipSuccess) e = vec(c->st.t_mu, src->st.t_mu, 8);
     if (e == hipSuccess) e = vec(c->st.t_leaps, src->st.t_leaps, 4);
     if (e == hipSuccess) e = vec(c->st.t_acc, src->st.t_acc, 4);
     if (e == hipSuccess) e = vec(c->st.t_prop, src->st.t_prop, 4);
@@ -1013,6 +1069,8 @@ extern "C" int mcmc_chains_fork(mcmc_chains* src, int64_t first, int64_t count, 
     }
     e = hipStreamSynchronize(st);
     if (e != hipSuccess) return bail(e);
+    HIP_TRY(hipMemsetAsync(c->d_evals, 0, sizeof(unsigned long long), st));   // NUTS: create's epsilon search counted
+    HIP_TRY(hipStreamSynchronize(st));
     c->steps_done = src->steps_done;
     c->spl = src->spl;
     c->store_grads = src->store_grads;
@@ -1084,7 +1142,15 @@ extern "C" int mcmc_chains_tuner_state(mcmc_chains* c, double* step, double* ste
         else std::fill(step, step + C, __builtin_nan(""));
     }
     if (step_bar) {
-        if (c->st.t_bar) HIP_TRY(get(step_bar, c->st.t_bar, C * 8));
+        if (c->sa.kind == SK_NUTS) {                            // exp(log epsilon_bar), the device's exp
+            double* tmp = nullptr;
+            if (int r = dmalloc(&tmp, C)) return r;
+            hipError_t e = mcmc_detmath(1, (int64_t)C, c->st.t_bar, c->st.t_bar, tmp, ctx->stream);
+            if (e == hipSuccess) e = get(step_bar, tmp, C * 8);
+            (void)hipStreamSynchronize(ctx->stream);
+            dfree(tmp);
+            HIP_TRY(e);
+        } else if (c->st.t_bar) HIP_TRY(get(step_bar, c->st.t_bar, C * 8));
         else std::fill(step_bar, step_bar + C, __builtin_nan(""));
     }
     if (nleaps) {
@@ -1187,6 +1253,21 @@ extern "C" int mcmc_chains_store_leaps(mcmc_chains* c, int64_t cap, double* pars
     return MCMC_OK;
 }
 
+extern "C" int mcmc_chains_nuts_diagnostics(mcmc_chains* c, double* epsilon, int32_t* ndoublings, int32_t on_device) {
+    if (!c) return fail(MCMC_E_INVALID_ARG, "NULL chains");
+    if (epsilon == nullptr) {
+        c->nuts_eps = nullptr;
+        c->nuts_nd = nullptr;
+        return MCMC_OK;
+    }
+    if (c->sa.kind != SK_NUTS) return fail(MCMC_E_INVALID_ARG, "the NUTS diagnostics need a NUTS sampler");
+    if (!ndoublings) return fail(MCMC_E_INVALID_ARG, "bad NUTS diagnostics buffers");
+    c->nuts_eps = epsilon;
+    c->nuts_nd = ndoublings;
+    c->nuts_on_device = on_device != 0;
+    return MCMC_OK;
+}
+
 // ------------------------------------------------------------------ run
 // device -> host copy of `rows` rows of `width` bytes from a packed device array into a host array whose
 // rows are `dpitch` bytes apart (dpitch == width: one contiguous copy)
@@ -1211,6 +1292,7 @@ int mcmc_run_serialmc_ld(mcmc_chains* c, const mcmc_runner_cfg* r, mcmc_outputs*
     if (ldc < c->C) return fail(MCMC_E_INVALID_ARG, "output leading dimension below the chain count");
     if (out && out->on_device && ldc != c->C)
         return fail(MCMC_E_INVALID_ARG, "strided outputs are host buffers");
+    if (c->h_lpars != nullptr && c->sa.kind == SK_NUTS) return fail(MCMC_E_INVALID_ARG, "storeLeaps needs an HMC or HMCDA sampler");
     if (int rc = mcmc_runner_validate(r)) return rc;
     mcmc_model* m = c->model;
     mcmc_ctx* ctx = m->ctx;
@@ -1305,6 +1387,19 @@ int mcmc_run_serialmc_ld(mcmc_chains* c, const mcmc_runner_cfg* r, mcmc_outputs*
         c->last_order = true;
     }
 
+    // NUTS diagnostics of the kept steps: straight into the caller's device buffers, or staged
+    const bool ndiag = c->sa.kind == SK_NUTS && c->nuts_eps != nullptr;
+    if (ndiag) {
+        const size_t nd = (size_t)nkept * (size_t)C;
+        if (c->nuts_on_device) {
+            s.nuts_eps = c->nuts_eps;
+            s.nuts_nd = c->nuts_nd;
+        } else {
+            if (int rc = ensure(c->nuts_buf, nd * 12)) return rc;
+            s.nuts_eps = (double*)c->nuts_buf.p;
+            s.nuts_nd = (int32_t*)(s.nuts_eps + nd);
+        }
+    }
     // storeLeaps: one step per launch; before each kept step, a record launch of its trajectory
     const bool rec = c->h_lpars != nullptr;
     const int64_t spl = rec ? 1 : launch_steps(c, r->len);
@@ -1361,6 +1456,15 @@ int mcmc_run_serialmc_ld(mcmc_chains* c, const mcmc_runner_cfg* r, mcmc_outputs*
         HIP_TRY(d2h(ctx, c->h_lH, dl + 3 * nk * lsz + nk * lsc, nk * lsc * 8));
         HIP_TRY(d2h(ctx, c->h_lnl, dl + 3 * nk * lsz + 2 * nk * lsc, nk * (size_t)C * 4));
         c->h_lpars = nullptr;                          // one run consumes the registration
+    }
+    if (ndiag) {
+        if (!c->nuts_on_device) {
+            const size_t nd = (size_t)nkept * (size_t)C;
+            HIP_TRY(d2h(ctx, c->nuts_eps, s.nuts_eps, nd * 8));
+            HIP_TRY(d2h(ctx, c->nuts_nd, s.nuts_nd, nd * 4));
+        }
+        c->nuts_eps = nullptr;                         // one run consumes the registration
+        c->nuts_nd = nullptr;
     }
 
     if (out) {
@@ -1457,6 +1561,9 @@ extern "C" int mcmc_run_seqmc(mcmc_chains* const* targets, int32_t ntargets, int
             return fail(MCMC_E_INVALID_ARG, "Models do not have the same parameter vector size");  // SeqMC.jl:49
         if (targets[t]->model->ctx != ctx) return fail(MCMC_E_INVALID_ARG, "targets live on different contexts");
         if (targets[t]->C != npart) return fail(MCMC_E_INVALID_ARG, "every target needs nchains == npart");
+        if (targets[t]->sa.kind == SK_NUTS)
+            return fail(MCMC_E_UNSUPPORTED, "SeqMC does not run NUTS targets: NUTS adapts epsilon by its own step counter "
+                                            "(NUTS.jl:166), which a population runner's resets do not carry");
     }
     if (cfg->steps > 0xffffffffLL) return fail(MCMC_E_INVALID_ARG, "steps exceed 2^32");
     if (int r = set_device(ctx)) return r;

@@ -24,6 +24,13 @@ hipError_t mcmc_lpc_ram_normal(const mcmc::KernelArgs& a, hipStream_t st);
 hipError_t mcmc_lpc_ram_absnormal(const mcmc::KernelArgs& a, hipStream_t st);
 hipError_t mcmc_lpc_ram_dist(const mcmc::KernelArgs& a, hipStream_t st);
 hipError_t mcmc_lpc_ram_ou(const mcmc::KernelArgs& a, hipStream_t st);      // lpc_ram_ou.hip
+// NUTS kernels, d <= 32 (nuts_<model>.hip): the step loop, or with init the initial epsilon search
+hipError_t mcmc_nuts_iso(const mcmc::KernelArgs& a, int init, hipStream_t st);
+hipError_t mcmc_nuts_normal(const mcmc::KernelArgs& a, int init, hipStream_t st);
+hipError_t mcmc_nuts_absnormal(const mcmc::KernelArgs& a, int init, hipStream_t st);
+hipError_t mcmc_nuts_dist(const mcmc::KernelArgs& a, int init, hipStream_t st);
+hipError_t mcmc_nuts_distobs(const mcmc::KernelArgs& a, int init, hipStream_t st);
+hipError_t mcmc_nuts_ou(const mcmc::KernelArgs& a, int init, hipStream_t st);
 // wave-per-chain RAM kernels, 32 < d <= 1024 (wpc_ram.hip)
 hipError_t mcmc_wpc_ram_iso(const mcmc::KernelArgs& a, hipStream_t st);
 hipError_t mcmc_wpc_ram_normal(const mcmc::KernelArgs& a, hipStream_t st);

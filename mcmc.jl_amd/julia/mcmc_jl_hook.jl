@@ -3,7 +3,7 @@
 # Target: the Julia the reference package is written for (Julia 0.3 syntax: `immutable`/`type`, `Union(...)`,
 # `{...}` Any-dicts, `Ptr{Void}`, `Uint8`, `finalizer(x, f)`, tasks with produce/consume).  It is include()d into
 # module MCMC, after src/runners/SerialMC.jl (INTEGRATION.md §Julia hook shows the one line), so it sees MCMCModel,
-# MCMCTask, MCMCChain, MCMCSample, HMCSample, SerialMC, RWM, MALA, HMC, HMCDA, RAM and EmpiricalMCMCTuner directly.
+# MCMCTask, MCMCChain, MCMCSample, HMCSample, SerialMC, RWM, MALA, HMC, HMCDA, RAM, NUTS and EmpiricalMCMCTuner directly.
 # For Julia >= 1.0 hosts without MCMC.jl, MCMCHip.jl is the plain binding of the same C ABI.
 #
 # What it replaces, with no edit to the reference's own files:
@@ -139,7 +139,7 @@ function hip_desc(m::MCMCHipModel, Xr::Vector{Float64})
                (m.kind == :dist || m.kind == :dist_obs) ? HIP_DISTS[m.dist] : 0)
 end
 
-# ---- samplers (RWM.jl:24-36, MALA.jl:50-62, HMC.jl:53-74, HMCDA.jl:24-43, RAM.jl:22-35)
+# ---- samplers (RWM.jl:24-36, MALA.jl:50-62, HMC.jl:53-74, HMCDA.jl:24-43, RAM.jl:22-35, NUTS.jl:30-43)
 hip_tuner(t) = t == nothing ? (0, 0, 0, 0., 0.) :
   (1, t.adaptStep, t.maxStep, t.targetPath, t.targetRate)      # EmpiricalMCMCTuner (samplers.jl:32-50)
 hip_cfg(kind, scale, drift, nl, ls, rate, len, shr, t0, st, tu, maxl) =
@@ -150,6 +150,14 @@ hip_sampler(s::MALA) = hip_cfg(2, 0., s.driftStep, 0, 0., 0., 0., 0., 0., 0., hi
 hip_sampler(s::HMC) = hip_cfg(3, 0., 0., s.nLeaps, s.leapStep, 0., 0., 0., 0., 0., hip_tuner(s.tuner), 0)
 hip_sampler(s::HMCDA) = hip_cfg(4, 0., 0., 0, 0., s.rate, s.len, s.shrinkage, s.t0, s.step, hip_tuner(nothing), 0)
 hip_sampler(s::RAM) = hip_cfg(5, s.scale, 0., 0, 0., s.rate, 0., 0., 0., 0., hip_tuner(nothing), 0)
+# NUTS (MCMC_NUTS = 6): n_leaps carries maxdoublings; built for d <= 32 and maxdoublings <= 10 (the library answers
+# MCMC_E_UNSUPPORTED beyond), NUTSTuner is abstract in the reference
+hip_sampler(s::NUTS) = (s.tuner == nothing || error("NUTS tuners are not built for the GPU");
+                        hip_cfg(6, 0., 0., s.maxdoublings, 0., 0., 0., 0., 0., 0., hip_tuner(nothing), 0))
+hip_is_nuts(s::MCMCSampler) = isa(s, NUTS)
+# SeqMC: NUTS adapts epsilon by its own step counter, so its targets stay on the reference path
+hip_seqmc_able(s::MCMCSampler) = true
+hip_seqmc_able(s::NUTS) = false
 
 # storeLeaps (HMC.jl:145-150, HMCDA.jl:110-117): leapfrog states recorded per step, up to a cap -- the trajectory
 # length for HMC (the tuner's maxStep bound when tuned), hip_leap_cap for HMCDA, whose length round(len / leapStep)
@@ -260,7 +268,8 @@ end
 # one mcmc_run_serialmc of `len` steps, rows (burnin+1):thinning:len kept: samples / gradients [nkept*d*C]
 # ([nkept][d][C] in C order = Julia (C, d, nkept) column-major), accept bits [nkept][ceil(C/64)], the final state
 # (C, d) and log-targets; with cap >= 0 the storeLeaps record of every kept step (mcmc_chains_store_leaps):
-# pars / grad / m as Julia (C, d, cap+1, nkept), logTarget / H (C, cap+1, nkept), nleaps (C, nkept)
+# pars / grad / m as Julia (C, d, cap+1, nkept), logTarget / H (C, cap+1, nkept), nleaps (C, nkept); with nuts the
+# NUTS diagnostics of every kept step (mcmc_chains_nuts_diagnostics): leaps[:epsilon], leaps[:ndoublings] (C, nkept)
 type HipRun
   x::Array{Float64, 3}
   g::Array{Float64, 3}
@@ -281,7 +290,7 @@ function hip_out_arrays(C::Int, d::Int, nk::Int, grads::Bool)
   x, g, bits, fx, flp
 end
 
-function hip_run!(ch::HipChains, burnin::Int, thinning::Int, len::Int, grads::Bool, cap::Int=-1)
+function hip_run!(ch::HipChains, burnin::Int, thinning::Int, len::Int, grads::Bool, cap::Int=-1, nuts::Bool=false)
   nk = length((burnin + 1):thinning:len)
   C, d = ch.nchains, ch.d
   x, g, bits, fx, flp = hip_out_arrays(C, d, nk, grads)
@@ -293,6 +302,12 @@ function hip_run!(ch::HipChains, burnin::Int, thinning::Int, len::Int, grads::Bo
     hipcheck(ccall((:mcmc_chains_store_leaps, hiplib), Cint,
                    (Ptr{Void}, Int64, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}),
                    ch.h, cap, leaps[:pars], leaps[:grad], leaps[:m], leaps[:logTarget], leaps[:H], leaps[:nleaps]))
+  end
+  if nuts                                                # diagnostics "epsilon" / "ndoublings" (NUTS.jl:177)
+    leaps[:epsilon] = Array(Float64, C, nk)
+    leaps[:ndoublings] = Array(Int32, C, nk)
+    hipcheck(ccall((:mcmc_chains_nuts_diagnostics, hiplib), Cint, (Ptr{Void}, Ptr{Float64}, Ptr{Int32}, Int32),
+                   ch.h, leaps[:epsilon], leaps[:ndoublings], 0))
   end
   out = HipOutputs(pointer(x), grads ? pointer(g) : convert(Ptr{Float64}, C_NULL), pointer(bits),
                    pointer(fx), pointer(flp), 0, 0., 0., 0)
@@ -346,7 +361,19 @@ function hip_run_group(m::MCMCHipModel, s::MCMCSampler, r::SerialMC, n::Int, see
   end
 end
 
-has_grads(s::MCMCSampler) = isa(s, MALA) || isa(s, HMC) || isa(s, HMCDA)
+has_grads(s::MCMCSampler) = isa(s, MALA) || isa(s, HMC) || isa(s, HMCDA) || isa(s, NUTS)
+# the sampler's own diagnostics of kept step j, chain c: {"accept"} for the Metropolis samplers, NUTS's
+# {"epsilon", "ndoublings"} (NUTS.jl:177, which has no "accept")
+function hip_step_diag(s::MCMCSampler, o::HipRun, j::Int, c::Int)
+  diag = Dict{Any, Any}()
+  if hip_is_nuts(s)
+    diag["epsilon"] = o.leaps[:epsilon][c, j]
+    diag["ndoublings"] = int(o.leaps[:ndoublings][c, j])
+  else
+    diag["accept"] = hip_accept(o, j, c)
+  end
+  diag
+end
 
 # diagnostics["leaps"] of kept step j, chain c: the reference's leapStates, HMCSample(pars, grad, m, logTarget, H)
 # for leap 0 (state0 after update!) .. nLeaps
@@ -429,22 +456,20 @@ function hip_produce_loop(st::HipTaskState)
   while true
     ch = hip_ensure!(st)
     if st.single
-      o = hip_run!(ch, 0, 1, 1, grads, cap)
-      diag = Dict{Any, Any}()
-      diag["accept"] = hip_accept(o, 1, 1)
+      o = hip_run!(ch, 0, 1, 1, grads, cap, hip_is_nuts(st.sampler))
+      diag = hip_step_diag(st.sampler, o, 1, 1)
       cap >= 0 && (diag["leaps"] = hip_leap_states(o, 1, 1, cap))
       x1, lp1 = vec(o.fx[1, :]), o.flp[1]
       produce(MCMCSample(x1, lp1, grads ? vec(o.g[1, :, 1]) : nothing, st.x, st.lp, nothing, diag))
       st.x, st.lp = x1, lp1
     else
       if st.buf == nothing || st.pos > size(st.buf.x, 3)
-        st.buf = hip_run!(ch, 0, 1, hip_chunk_len(st, cap), grads, cap)
+        st.buf = hip_run!(ch, 0, 1, hip_chunk_len(st, cap), grads, cap, hip_is_nuts(st.sampler))
         st.pos = 1
       end
       o, j = st.buf, st.pos
       st.pos += 1
-      diag = Dict{Any, Any}()
-      diag["accept"] = hip_accept(o, j, 1)
+      diag = hip_step_diag(st.sampler, o, j, 1)
       cap >= 0 && (diag["leaps"] = hip_leap_states(o, j, 1, cap))
       produce(MCMCSample(vec(o.x[1, :, j]), NaN, grads ? vec(o.g[1, :, j]) : nothing, nan, NaN, nothing, diag))
     end
@@ -475,13 +500,20 @@ function hip_colnames(m::MCMCHipModel)
 end
 
 # chain c of a batched run, built like run_serialmc's (SerialMC.jl:37-85): samples / gradients DataFrames with the
-# pmap column names, diagnostics {"step" => collect(r), "accept" => Bool[] (, "leaps")}, the batch's runTime
+# pmap column names, diagnostics {"step" => collect(r), "accept" => Bool[] (, "leaps")} -- for NUTS
+# {"step", "epsilon", "ndoublings"}; a group run does not gather those two --, the batch's runTime
 function hip_chain(m::MCMCHipModel, s::MCMCSampler, r::SerialMC, o::HipRun, c::Int, t::MCMCTask)
   cn = hip_colnames(m)
   nk = size(o.x, 3)
   sc = reshape(o.x[c, :, :], m.size, nk)'                               # nkept x d
   gd = has_grads(s) ? DataFrame(reshape(o.g[c, :, :], m.size, nk)', cn) : DataFrame()
-  diags = {"step" => collect(r.r), "accept" => Bool[hip_accept(o, j, c) for j in 1:nk]}
+  diags = {"step" => collect(r.r)}
+  if !hip_is_nuts(s)
+    diags["accept"] = Bool[hip_accept(o, j, c) for j in 1:nk]
+  elseif haskey(o.leaps, :epsilon)
+    diags["epsilon"] = Float64[o.leaps[:epsilon][c, j] for j in 1:nk]
+    diags["ndoublings"] = Int[o.leaps[:ndoublings][c, j] for j in 1:nk]
+  end
   if hip_store_leaps(s)
     cap = hip_leaps_cap(s)
     diags["leaps"] = Array{HMCSample}[hip_leap_states(o, j, c, cap) for j in 1:nk]
@@ -521,7 +553,7 @@ function hip_run_tasks(t::Array{MCMCTask}, stop::Bool, devs::Vector{Int32}=Int32
   else
     ch = hip_chains(m, s, n, seed, first)
     cap = hip_store_leaps(s) ? hip_leaps_cap(s) : -1
-    o = hip_run!(ch, r.burnin, r.thinning, r.len, has_grads(s), cap)
+    o = hip_run!(ch, r.burnin, r.thinning, r.len, has_grads(s), cap, hip_is_nuts(s))
   end
   res = Array(MCMCChain, size(t))
   for k in 1:n
@@ -567,6 +599,7 @@ function hip_seqmc_able(t::Array{MCMCTask})
   isempty(t) && return false
   for x in t
     (isa(x.model, MCMCHipModel) && haskey(hip_tasks, x.task)) || return false
+    hip_seqmc_able(x.sampler) || return false               # NUTS targets: the reference's run_seqmc
     st = hip_tasks[x.task]
     (st.chains == nothing && st.src == nothing && !st.stopped) || return false
   end

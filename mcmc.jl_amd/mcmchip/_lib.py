@@ -40,6 +40,7 @@ SAMPLER_MALA = 2
 SAMPLER_HMC = 3
 SAMPLER_HMCDA = 4
 SAMPLER_RAM = 5
+SAMPLER_NUTS = 6
 
 VAR_IMSE = 1
 VAR_IPSE = 2
@@ -55,7 +56,8 @@ EXPORTED_SYMBOLS = (
     "mcmc_chains_ram_factor", "mcmc_chains_tuner_state",
     "mcmc_chains_set_steps_per_launch", "mcmc_chains_set_store_gradients", "mcmc_chains_set_tuner_burnin",
     "mcmc_chains_reserve_outputs",
-    "mcmc_chains_launches", "mcmc_chains_step_kernel", "mcmc_chains_store_leaps", "mcmc_run_serialmc",
+    "mcmc_chains_launches", "mcmc_chains_step_kernel", "mcmc_chains_store_leaps", "mcmc_chains_nuts_diagnostics",
+    "mcmc_run_serialmc",
     "mcmc_group_create", "mcmc_group_destroy", "mcmc_group_size", "mcmc_group_plan", "mcmc_group_chains_create",
     "mcmc_group_chains_destroy", "mcmc_group_chains_reset", "mcmc_group_chains_steps_done",
     "mcmc_group_chains_set_steps_per_launch", "mcmc_group_chains_block", "mcmc_group_run_serialmc",
@@ -164,6 +166,7 @@ def load() -> ct.CDLL:
         "mcmc_chains_step_kernel": (ct.c_int, [P, ct.c_char_p, i64]),
         "mcmc_chains_store_leaps": (ct.c_int, [P, i64, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p,
                                                ct.c_void_p, ct.c_void_p]),
+        "mcmc_chains_nuts_diagnostics": (ct.c_int, [P, ct.c_void_p, ct.c_void_p, i32]),
         "mcmc_run_serialmc": (ct.c_int, [P, ct.POINTER(RunnerCfg), ct.POINTER(Outputs)]),
         "mcmc_group_create": (ct.c_int, [ct.POINTER(ct.c_int32), i32, pp]),
         "mcmc_group_destroy": (ct.c_int, [P]),

@@ -3,7 +3,8 @@
 Names, argument meaning and error behaviour follow the reference:
 
   model(f; init, scale, grad)    src/modellers/mcmcmodels.jl:27-33, likmodel.jl:100-143
-  RWM, MALA, HMC, HMCDA, RAM     src/samplers/{RWM,MALA,HMC,HMCDA,RAM}.jl (constructors + @asserts)
+  RWM, MALA, HMC, HMCDA, RAM,    src/samplers/{RWM,MALA,HMC,HMCDA,RAM,NUTS}.jl (constructors + @asserts)
+  NUTS
   EmpMCTuner                     src/samplers/samplers.jl:32-50
   SerialMC(steps, burnin, thinning) / SerialMC(range)   src/runners/SerialMC.jl:12-35
   m * s * r -> MCMCTask          src/MCMC.jl:87-98
@@ -32,7 +33,7 @@ from ._lib import check, dptr
 __all__ = [
     "IsoNormalDot", "NormalDSL", "AbsNormalDSL", "DistDSL", "DistObsDSL", "LogisticRegression", "LinearRegression", "ProbitRegression", "vaso_data",
     "OrnsteinUhlenbeck", "ou_series", "MCMCLikelihoodModel", "model",
-    "RWM", "MALA", "HMC", "HMCDA", "RAM", "EmpMCTuner", "EmpiricalMCMCTuner", "SerialMC", "MCMCTask", "MCMCChain",
+    "RWM", "MALA", "HMC", "HMCDA", "RAM", "NUTS", "EmpMCTuner", "EmpiricalMCMCTuner", "SerialMC", "MCMCTask", "MCMCChain",
     "run", "resume", "device_count",
 ]
 
@@ -463,6 +464,43 @@ class RAM(_Sampler):
         return c
 
 
+class NUTS(_Sampler):
+    """The No-U-Turn sampler (NUTS.jl:30-43): NUTS(), NUTS(maxdoublings), NUTS(maxdoublings, tuner),
+    NUTS(maxdoublings=..., tuner=...).  Each chain adapts its own epsilon by dual averaging over its first 1 000
+    steps (NUTS.jl:166-173).  A run's diagnostics hold "epsilon" and "ndoublings" per kept step (NUTS.jl:177).
+    Built for targets with d <= 32 and maxdoublings <= 10; NUTSTuner is abstract in the reference, so a tuner other
+    than None is refused."""
+    kind = _lib.SAMPLER_NUTS
+
+    def __init__(self, *args, maxdoublings: Optional[int] = None, tuner=None):
+        a = list(args)
+        if len(a) > 2:
+            raise TypeError("NUTS(maxdoublings[, tuner])")
+        md = 5                                                  # NUTS(i::Int=5) = NUTS(i, nothing)
+        if a and not isinstance(a[0], (int, np.integer)):       # NUTS(t::NUTSTuner) = NUTS(5, t)
+            tuner = a.pop(0)
+            if a:
+                raise TypeError("NUTS(maxdoublings[, tuner])")
+        if a:
+            md = int(a.pop(0))
+        if a:
+            tuner = a.pop(0)
+        if maxdoublings is not None:
+            md = int(maxdoublings)
+        if not md > 0:
+            raise AssertionError("max doublings should be > 0")               # NUTS.jl:35
+        if not md < 20:
+            raise AssertionError("max doublings reasonably be < 20")          # NUTS.jl:36
+        if tuner is not None:
+            raise NotImplementedError("NUTSTuner is abstract in the reference (NUTS.jl:22)")
+        self.maxdoublings = md
+
+    def cfg(self):
+        c = super().cfg()
+        c.n_leaps = self.maxdoublings                           # mcmc_sampler_cfg.n_leaps carries maxdoublings
+        return c
+
+
 # ------------------------------------------------------------------ runner
 class SerialMC:
     """SerialMC runner (SerialMC.jl:12-35): keeps samples i in r = (burnin+1):thinning:steps."""
@@ -765,18 +803,23 @@ class MCMCChain:
         self.runTime = runTime
         self.kernel_ms = kernel_ms
         self.final_x, self.final_lp = final_x, final_lp
+        self.moved = None                       # NUTS: the kept steps' accept bits [C, nkept] (no "accept" diagnostic)
 
     def _chains(self, first: int, count: int, task: "MCMCTask") -> "MCMCChain":
         """Chains [first, first + count) of this result as the result of `task`."""
         sl = slice(first, first + count)
         diags = dict(self.diagnostics)
-        diags["accept"] = self.diagnostics["accept"][sl]
+        for k in ("accept", "epsilon", "ndoublings"):           # per-chain diagnostics [C, nkept]
+            if k in diags:
+                diags[k] = self.diagnostics[k][sl]
         if "leaps" in diags:
             diags["leaps"] = {k: v[..., sl] for k, v in self.diagnostics["leaps"].items()}
         g = None if self._gradients is None else self._gradients[:, :, sl]
         fx = None if self.final_x is None else self.final_x[:, sl]
         flp = None if self.final_lp is None else self.final_lp[sl]
-        return MCMCChain(self.range, self._samples[:, :, sl], g, diags, task, self.runTime, self.kernel_ms, fx, flp)
+        ch = MCMCChain(self.range, self._samples[:, :, sl], g, diags, task, self.runTime, self.kernel_ms, fx, flp)
+        ch.moved = None if self.moved is None else self.moved[sl]
+        return ch
 
     @property
     def samples(self) -> np.ndarray:
@@ -843,6 +886,10 @@ def _run_task(t: MCMCTask) -> MCMCChain:
                  "H": np.empty((nk, cap + 1, C)), "nleaps": np.empty((nk, C), dtype=np.int32)}
         check(lib.mcmc_chains_store_leaps(h, cap, *(leaps[k].ctypes.data for k in
                                                     ("pars", "grad", "m", "logTarget", "H", "nleaps"))))
+    nuts = None
+    if t.sampler.kind == _lib.SAMPLER_NUTS and t.devices is None:   # NUTS.jl:177 (a group run does not gather them)
+        nuts = (np.empty((nk, C)), np.empty((nk, C), dtype=np.int32))
+        check(lib.mcmc_chains_nuts_diagnostics(h, nuts[0].ctypes.data, nuts[1].ctypes.data, 0))
     cfg = r.cfg()
     gather_s = None
     if t.devices is not None:
@@ -852,13 +899,22 @@ def _run_task(t: MCMCTask) -> MCMCChain:
     else:
         check(lib.mcmc_run_serialmc(h, ct.byref(cfg), ct.byref(out)))
     diags = {"step": list(r.r), "accept": _unpack_bits(bits, C)}
+    moved = None
+    if t.sampler.kind == _lib.SAMPLER_NUTS:
+        # the reference's keys (NUTS.jl:177): no "accept"; the accept bits (1: some doubling's candidate was taken)
+        # stay readable as chain.moved [C, nkept]
+        moved = diags.pop("accept")
+        if nuts is not None:
+            diags["epsilon"], diags["ndoublings"] = nuts[0].T.copy(), nuts[1].T.copy()
     if gather_s is not None:
         diags["gather_s"] = gather_s                         # end gather of the group run, timed apart
     if leaps is not None:
         # per kept step: the trajectory's states, leap 0 = state0 (the reference's leapStates array of
         # HMCSample(pars, grad, m, logTarget, H)), NaN past nleaps
         diags["leaps"] = leaps
-    return MCMCChain(r.r, samples, grads, diags, t, out.runtime_s, out.kernel_ms, fx, flp)
+    ch = MCMCChain(r.r, samples, grads, diags, t, out.runtime_s, out.kernel_ms, fx, flp)
+    ch.moved = moved
+    return ch
 
 
 def _same_task_kind(t: MCMCTask, t0: MCMCTask) -> bool:
