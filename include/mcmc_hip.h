@@ -344,6 +344,20 @@ enum { MCMC_VAR_IMSE = 1, MCMC_VAR_IPSE = 2, MCMC_VAR_BM = 3 };
 int mcmc_stats_ess(mcmc_ctx* ctx, const double* samples, int64_t nkept, int64_t d, int64_t nchains, int32_t vtype,
                    int64_t maxlag, int64_t batchlen, int32_t on_device, double* ess, double* var);
 
+/* Zero-variance control-variate estimators (src/stats/zv.jl:8-68) of every chain of samples / grads
+ * [nkept][d][nchains].  With z = -grads/2 and w_t the k control variates of kept step t -- MCMC_ZV_LINEAR: k = d,
+ * w = z; MCMC_ZV_QUADRATIC: k = d(d+3)/2, the z_j, then 2 z_j x_j - 1, then x_i z_j + x_j z_i for i < j in zv.jl's
+ * loop order -- a = -cov(w)^-1 cov(w, x) per chain and zv[t][j] = x[t][j] + sum_i w[t][i] a[i][j].  Built for
+ * d <= 32 (linear) and d <= 8 (quadratic); wider answers MCMC_E_UNSUPPORTED.  nkept <= k answers
+ * MCMC_E_INVALID_ARG.  A chain whose Gram matrix is not positive definite gets info[c] = the 1-based index of the
+ * failing pivot and NaN in its zv and coef columns; info[c] = 0 otherwise.  Two things mark it: fewer than k kept
+ * steps that differ from the step before (the matrix then has rank <= moves < k whatever rounding leaves behind:
+ * info[c] = moves + 1, so a chain that never moved always gets 1), or a Cholesky pivot <= 0 or not finite.  coef [k][d][nchains] and info [nchains] may be NULL.  on_device != 0: every pointer is
+ * device memory on ctx's GPU. */
+enum { MCMC_ZV_LINEAR = 1, MCMC_ZV_QUADRATIC = 2 };
+int mcmc_stats_zv(mcmc_ctx* ctx, int32_t order, const double* samples, const double* grads, int64_t nkept, int64_t d,
+                  int64_t nchains, int32_t on_device, double* zv, double* coef, int32_t* info);
+
 /* ---- diagnostics used by the parity tests: evaluate the build's deterministic
  *      math on the device.  op: 0 log, 1 exp, 2 sin2pi, 3 cos2pi,
  *      4 sqrt, 5 div(x, y), 6 normals (x = block counters), 7 Julia-0.2 round,

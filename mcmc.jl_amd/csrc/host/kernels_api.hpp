@@ -64,6 +64,12 @@ hipError_t mcmc_seqmc_store(int64_t N, int d, const double* pars, const double* 
 // effective sample size of every (parameter, chain) series of samples [n][d][C] (stats.hip)
 hipError_t mcmc_launch_ess(const double* samples, int64_t n, int64_t d, int64_t C, int32_t vtype, int64_t maxlag,
                            int64_t batchlen, double* ess, double* var, hipStream_t st);
+// zero-variance estimators (zv.hip): order 1 linear, 2 quadratic; samples x and gradients g [n][d][C] -> zv [n][d][C],
+// coef [k][d][C] (or NULL), info [C] (or NULL).  d <= mcmc_zv_max_d(order); k = mcmc_zv_k(order, d)
+hipError_t mcmc_launch_zv(int order, const double* x, const double* g, int64_t n, int d, int64_t C, double* zv,
+                          double* coef, int32_t* info, hipStream_t st);
+int mcmc_zv_max_d(int order);
+int64_t mcmc_zv_k(int order, int64_t d);
 // padded coordinate count of the regression kernels; their 16-chain tiles per workgroup
 int mcmc_glm_d_pad(int d);
 int mcmc_glm_tiles_per_wg(int d);

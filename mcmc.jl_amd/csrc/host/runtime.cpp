@@ -1681,6 +1681,62 @@ extern "C" int mcmc_stats_ess(mcmc_ctx* ctx, const double* samples, int64_t nkep
     return rc;
 }
 
+extern "C" int mcmc_stats_zv(mcmc_ctx* ctx, int32_t order, const double* samples, const double* grads, int64_t nkept,
+                             int64_t d, int64_t nchains, int32_t on_device, double* zv, double* coef, int32_t* info) {
+    if (!ctx || !samples || !grads || !zv) return fail(MCMC_E_INVALID_ARG, "NULL argument");
+    if (order != MCMC_ZV_LINEAR && order != MCMC_ZV_QUADRATIC)
+        return fail(MCMC_E_INVALID_ARG, "Unknown ZV order " + std::to_string(order));
+    if (d <= 0 || nchains <= 0) return fail(MCMC_E_INVALID_ARG, "need d > 0, nchains > 0");
+    if (d > mcmc_zv_max_d(order))
+        return fail(MCMC_E_UNSUPPORTED, std::string(order == MCMC_ZV_LINEAR ? "linear" : "quadratic") +
+                                            " ZV is built for d <= " + std::to_string(mcmc_zv_max_d(order)) +
+                                            " (d = " + std::to_string(d) + ")");
+    const int64_t k = mcmc_zv_k(order, d);
+    if (nkept <= k)                                        // the centred Gram matrix has rank <= nkept - 1
+        return fail(MCMC_E_INVALID_ARG, "ZV needs nkept > k = " + std::to_string(k) + " control variates (nkept = " +
+                                            std::to_string(nkept) + ")");
+    if (int r = set_device(ctx)) return r;
+    hipStream_t st = ctx->stream;
+    const size_t ns = (size_t)nkept * (size_t)d * (size_t)nchains, nc = (size_t)k * (size_t)d * (size_t)nchains;
+    const double *dx = samples, *dg = grads;
+    double *dxb = nullptr, *dgb = nullptr, *dzb = nullptr, *dcb = nullptr, *dz = zv, *dc = coef;
+    int32_t *dib = nullptr, *di = info;
+    int rc = MCMC_OK;
+    do {
+        if (!on_device) {
+            if ((rc = dmalloc(&dxb, ns))) break;
+            if ((rc = dmalloc(&dgb, ns))) break;
+            if ((rc = dmalloc(&dzb, ns))) break;
+            if (coef && (rc = dmalloc(&dcb, nc))) break;
+            if (info && (rc = dmalloc(&dib, (size_t)nchains))) break;
+            if (h2d(ctx, dxb, samples, ns * 8) != hipSuccess || h2d(ctx, dgb, grads, ns * 8) != hipSuccess) {
+                rc = fail(MCMC_E_HIP, "samples / gradients upload failed");
+                break;
+            }
+            dx = dxb;
+            dg = dgb;
+            dz = dzb;
+            dc = dcb;
+            di = dib;
+        }
+        hipError_t e = mcmc_launch_zv(order, dx, dg, nkept, (int)d, nchains, dz, dc, di, st);
+        if (e == hipSuccess && !on_device) e = d2h(ctx, zv, dz, ns * 8);
+        if (e == hipSuccess && !on_device && coef) e = d2h(ctx, coef, dc, nc * 8);
+        if (e == hipSuccess && !on_device && info) e = d2h(ctx, info, di, (size_t)nchains * 4);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = fail(MCMC_E_HIP, std::string("zv: ") + hipGetErrorString(e));
+    } while (0);
+    if (!on_device) {
+        (void)hipStreamSynchronize(st);
+        dfree(dxb);
+        dfree(dgb);
+        dfree(dzb);
+        dfree(dcb);
+        dfree(dib);
+    }
+    return rc;
+}
+
 extern "C" int mcmc_debug_detmath(mcmc_ctx* ctx, int op, int64_t n, const double* x, const double* y, double* out) {
     if (!ctx || !x || !out || n <= 0) return fail(MCMC_E_INVALID_ARG, "bad argument");
     if (int r = set_device(ctx)) return r;

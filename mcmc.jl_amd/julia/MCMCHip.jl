@@ -114,6 +114,17 @@ function run_serialmc(ch, d, C; steps, burnin = 0, thinning = 1)
     smp, accept, out.runtime_s
 end
 
+# linearZv / quadraticZv (zv.jl:8-68) of every chain: samples and gradients of size (C, d, nkept) -> the ZV chains
+# (C, d, nkept), the coefficients (C, d, k) and info (C; nonzero: the chain's Gram matrix is not positive definite)
+function stats_zv(ctx, smp::Array{Float64,3}, grd::Array{Float64,3}; order = 1)
+    C, d, nk = size(smp)
+    k = order == 2 ? div(d * (d + 3), 2) : d
+    zv = Array{Float64}(undef, C, d, nk); coef = Array{Float64}(undef, C, d, k); info = zeros(Int32, C)
+    check(ccall((:mcmc_stats_zv, lib), Cint, (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int32,
+        Ptr{Float64}, Ptr{Float64}, Ptr{Int32}), ctx, order, smp, grd, nk, d, C, 0, zv, coef, info))
+    zv, coef, info
+end
+
 # ---- prun (runners.jl:35-42, examples/parallel_serialmc.jl) -> one chain batch over a node's GPUs
 # mcmc_group_*: contiguous 64-chain-aligned blocks, one per listed device, driven from this one Julia thread
 # (a library worker thread per block); results bit-identical to one context running every chain.  Blocks are whole

@@ -27,6 +27,8 @@
 #                                                  other arrays pmap as before;
 #   ess(cs::Array{MCMCChain})   ess.jl:6-10      -- a new method (the reference's ess(c::MCMCChain) is untouched):
 #                                                  the ESS of every chain of a GPU batch in one mcmc_stats_ess call.
+#   linearZv(cs::Array{MCMCChain}), quadraticZv(cs::Array{MCMCChain})   zv.jl:8-68 -- new methods likewise: the ZV
+#                                                  estimators of every chain of a GPU batch in one mcmc_stats_zv call.
 # Runner semantics.  A GPU task produces every step (run_serialmc applies the kept range itself), in chunks of at
 # most the task runner's len; the samplers' adaptation reads the task's own runner (MALA.jl:116, HMC.jl:167,
 # HMCDA.jl:133-141), so the task runner's burnin is set as the chains' tuner burnin (mcmc_chains_set_tuner_burnin)
@@ -41,7 +43,7 @@
 
 const hiplib = haskey(ENV, "MCMCHIP_LIB") ? ENV["MCMCHIP_LIB"] : "libmcmc_hip"
 
-export MCMCHipModel, hipmodel, hip_run_batch, hip_run_arrays, hip_srand, hip_ess
+export MCMCHipModel, hipmodel, hip_run_batch, hip_run_arrays, hip_srand, hip_ess, hip_zv
 
 # ---- C structs (include/mcmc_hip.h), isbits, C layout
 immutable HipModelDesc            # mcmc_model_desc
@@ -675,6 +677,44 @@ function ess(cs::Array{MCMCChain}; vtype::Symbol=:imse, maxlag::Int=0, batchlen:
   e, _ = hip_ess(x; vtype=vtype, maxlag=maxlag, batchlen=batchlen, device=cs[1].task.model.device)
   [vec(e[c, :]) for c in 1:length(cs)]
 end
+
+# ---- ZV estimators on the device (zv.jl:8-68; mcmc_stats_zv)
+const HIP_ZV_ORDERS = {:linear => 1, :quadratic => 2}
+
+# samples and gradients as hip_run_arrays returns them, (C, d, nkept): the ZV chains (C, d, nkept), the coefficients
+# (C, d, k) and info (C): nonzero for a chain whose Gram matrix is not positive definite (its values are NaN)
+function hip_zv(x::Array{Float64, 3}, g::Array{Float64, 3}; order::Symbol=:linear, device::Int=0)
+  @assert haskey(HIP_ZV_ORDERS, order) "Unknown ZV order $order"
+  @assert size(x) == size(g) "samples and gradients differ in size"
+  C, d, nk = size(x)
+  k = order == :quadratic ? div(d * (d + 3), 2) : d
+  z, a, info = Array(Float64, C, d, nk), Array(Float64, C, d, k), Array(Int32, C)
+  hipcheck(ccall((:mcmc_stats_zv, hiplib), Cint,
+                 (Ptr{Void}, Int32, Ptr{Float64}, Ptr{Float64}, Int64, Int64, Int64, Int32, Ptr{Float64}, Ptr{Float64},
+                  Ptr{Int32}),
+                 hip_context(device).h, HIP_ZV_ORDERS[order], x, g, nk, d, C, 0, z, a, info))
+  z, a, info
+end
+
+# linearZv(c) / quadraticZv(c) of every chain of an array, each as the reference returns it (zvChain nkept x d, a k x d);
+# chains of GPU tasks with equal shapes and stored gradients go to the device in one call, anything else chain by chain
+function hip_zv_chains(cs::Array{MCMCChain}, order::Symbol)
+  gpu = !isempty(cs) && all(c -> isa(c.task, MCMCTask) && isa(c.task.model, MCMCHipModel), cs)
+  if gpu
+    nk, d = size(cs[1].samples)
+    gpu = all(c -> size(c.samples) == (nk, d) && size(c.gradients) == (nk, d), cs)
+  end
+  if !gpu
+    return [order == :quadratic ? quadraticZv(c) : linearZv(c) for c in cs]
+  end
+  x = Float64[cs[c].samples[k, j] for c in 1:length(cs), j in 1:d, k in 1:nk]
+  g = Float64[cs[c].gradients[k, j] for c in 1:length(cs), j in 1:d, k in 1:nk]
+  z, a, _ = hip_zv(x, g; order=order, device=cs[1].task.model.device)
+  nc = size(a, 3)
+  [(Float64[z[c, j, k] for k in 1:nk, j in 1:d], Float64[a[c, j, i] for i in 1:nc, j in 1:d]) for c in 1:length(cs)]
+end
+linearZv(cs::Array{MCMCChain}) = hip_zv_chains(cs, :linear)
+quadraticZv(cs::Array{MCMCChain}) = hip_zv_chains(cs, :quadratic)
 
 # nchains independent chains as one batch, each returned MCMCChain's task continuing its own chain
 hip_run_batch(m::MCMCHipModel, s::MCMCSampler, r::SerialMC, nchains::Int) =

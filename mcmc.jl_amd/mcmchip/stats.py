@@ -8,6 +8,8 @@ mcvar_imse   var.jl:45-75         Geyer's initial monotone sequence estimator
 mcvar_ipse   var.jl:95-117        Geyer's initial positive sequence estimator
 var          var.jl:137-149       dispatch on vtype
 ess, actime  ess.jl:6-20          n * var_iid / var_vtype, var_vtype / var_iid
+linear_zv    zv.jl:8-28           zero-variance estimator, linear control variates
+quadratic_zv zv.jl:33-66          zero-variance estimator, quadratic control variates
 
 Autocovariances follow StatsBase.acf(x, lags, correlation=false): the demeaned
 sum sum_{t} z_t z_{t+k} / n.  They are computed by FFT over all chains and
@@ -22,7 +24,7 @@ from typing import Optional
 import numpy as np
 
 __all__ = ["acceptance", "mean", "mcvar_iid", "mcvar_bm", "mcvar_imse", "mcvar_ipse", "var", "ess", "actime",
-           "autocov", "ess_device", "ess_per_sec"]
+           "autocov", "ess_device", "ess_per_sec", "linear_zv", "quadratic_zv", "zv_device"]
 
 
 def _samples(c) -> np.ndarray:
@@ -171,3 +173,111 @@ def ess_per_sec(ess_dc, seconds: float) -> float:
     m = ess_dc.min(dim=0).values.sum().item() if hasattr(ess_dc, "min") and hasattr(ess_dc, "dim") \
         else float(np.min(ess_dc, axis=0).sum())
     return m / seconds
+
+
+def _samples_grads(c, grad=None):
+    """([C, nkept, d] samples, gradients) of an MCMCChain, or of two arrays."""
+    if grad is None:
+        if getattr(c, "_gradients", 0) is None or getattr(c, "gradients", None) is None:
+            raise ValueError("ZV estimators need the chain's gradients: run a gradient sampler (MALA, HMC, HMCDA, "
+                             "NUTS) with store_gradients on")
+        grad = c.gradients
+    s, g = _samples(c), _samples(grad)
+    if s.shape != g.shape:
+        raise ValueError(f"samples {s.shape} and gradients {g.shape} differ in shape")
+    return s, g
+
+
+def _zv(x: np.ndarray, w: np.ndarray):
+    """zv.jl:18-25 / :55-63 for one chain: x [n, d], control variates w [n, k] -> (x + w a, a [k, d])."""
+    d, k = x.shape[1], w.shape[1]
+    a = np.empty((k, d))
+    for i in range(d):
+        cov_all = np.atleast_2d(np.cov(np.column_stack([w, x[:, i]]), rowvar=False))
+        precision = np.linalg.inv(cov_all[:k, :k])
+        sigma = cov_all[:k, k]
+        a[:, i] = -precision @ sigma
+    return x + w @ a, a
+
+
+def linear_zv(c, grad=None):
+    """linearZv (zv.jl:8-30) per chain: (zv_chain [C, nkept, d], a [C, d, d])."""
+    s, g = _samples_grads(c, grad)
+    out = [_zv(x, -gr / 2) for x, gr in zip(s, g)]
+    return np.stack([o[0] for o in out]), np.stack([o[1] for o in out])
+
+
+def quadratic_zv(c, grad=None):
+    """quadraticZv (zv.jl:33-68) per chain: (zv_chain [C, nkept, d], a [C, d(d+3)/2, d])."""
+    s, g = _samples_grads(c, grad)
+    out = []
+    for x, gr in zip(s, g):
+        n, d = x.shape
+        z = -gr / 2
+        zq = np.empty((n, d * (d + 3) // 2))
+        zq[:, :d] = z
+        zq[:, d:2 * d] = 2 * z * x - 1
+        col = 2 * d
+        for i in range(d - 1):
+            for j in range(i + 1, d):
+                zq[:, col] = x[:, i] * z[:, j] + x[:, j] * z[:, i]
+                col += 1
+        out.append(_zv(x, zq))
+    return np.stack([o[0] for o in out]), np.stack([o[1] for o in out])
+
+
+def zv_device(c, order: int = 1, device: int = 0, return_coef: bool = False, return_info: bool = False):
+    """ZV estimators of every chain on the GPU (kernels/zv.hip; zv.jl:8-68); order 1 linear, 2 quadratic.
+
+    `c` is an MCMCChain (host arrays; returns numpy [nchains, nkept, d] like `samples`, coefficients
+    [nchains, k, d], info [nchains]) or a pair (samples, gradients) of contiguous float64 device tensors
+    [nkept, d, nchains] in the C-ABI layout (returns device tensors [nkept, d, nchains], [k, d, nchains], [nchains];
+    nothing crosses PCIe, and the result can go straight into `ess_device`).  info[c] != 0 marks a chain whose Gram
+    matrix is not positive definite; its values are NaN."""
+    from . import _lib
+    from .api import _ctx
+    if order not in (1, 2):
+        raise ValueError(f"Unknown ZV order {order}: 1 (linear) or 2 (quadratic)")
+    lib = _lib.load()
+
+    def pack(z, a, i):
+        out = (z,) + ((a,) if return_coef else ()) + ((i,) if return_info else ())
+        return out if len(out) > 1 else z
+
+    if isinstance(c, (tuple, list)) and len(c) == 2 and hasattr(c[0], "data_ptr"):
+        import torch
+        x, g = c
+        for t in (x, g):
+            if t.dim() != 3 or t.dtype != torch.float64 or not t.is_contiguous() or not t.is_cuda:
+                raise ValueError("expected contiguous float64 device tensors [nkept, d, nchains]")
+        if x.shape != g.shape or x.device != g.device:
+            raise ValueError("samples and gradients differ in shape or device")
+        n, d, C = x.shape
+        k = d * (d + 3) // 2 if order == 2 else d
+        z = torch.empty_like(x)
+        a = torch.empty((k, d, C), dtype=torch.float64, device=x.device) if return_coef else None
+        i = torch.empty((C,), dtype=torch.int32, device=x.device) if return_info else None
+        _lib.check(lib.mcmc_stats_zv(_ctx(x.device.index or 0), order, x.data_ptr(), g.data_ptr(), n, d, C, 1,
+                                     z.data_ptr(), a.data_ptr() if a is not None else None,
+                                     i.data_ptr() if i is not None else None))
+        return pack(z, a, i)
+    if hasattr(c, "_samples"):
+        if getattr(c, "_gradients", None) is None:
+            raise ValueError("ZV estimators need the chain's gradients: run a gradient sampler (MALA, HMC, HMCDA, "
+                             "NUTS) with store_gradients on")
+        x, g = c._samples, c._gradients
+    else:
+        x, g = c
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    g = np.ascontiguousarray(g, dtype=np.float64)
+    if x.ndim != 3 or x.shape != g.shape:
+        raise ValueError("expected samples and gradients [nkept, d, nchains] of one shape")
+    n, d, C = x.shape
+    k = d * (d + 3) // 2 if order == 2 else d
+    z = np.empty((n, d, C))
+    a = np.empty((k, d, C)) if return_coef else None
+    i = np.empty(C, dtype=np.int32) if return_info else None
+    _lib.check(lib.mcmc_stats_zv(_ctx(device), order, x.ctypes.data, g.ctypes.data, n, d, C, 0, z.ctypes.data,
+                                 a.ctypes.data if a is not None else None, i.ctypes.data if i is not None else None))
+    return pack(np.ascontiguousarray(z.transpose(2, 0, 1)),
+                np.ascontiguousarray(a.transpose(2, 0, 1)) if a is not None else None, i)
