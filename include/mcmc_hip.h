@@ -94,7 +94,7 @@ enum {
 };
 
 /* samplers */
-enum { MCMC_RWM = 1, MCMC_MALA = 2, MCMC_HMC = 3, MCMC_HMCDA = 4, MCMC_RAM = 5, MCMC_NUTS = 6 };
+enum { MCMC_RWM = 1, MCMC_MALA = 2, MCMC_HMC = 3, MCMC_HMCDA = 4, MCMC_RAM = 5, MCMC_NUTS = 6, MCMC_SMMALA = 7 };
 
 typedef struct mcmc_ctx mcmc_ctx;
 typedef struct mcmc_model mcmc_model;
@@ -102,7 +102,13 @@ typedef struct mcmc_chains mcmc_chains;
 
 typedef struct {
     int32_t kind;            /* MCMC_MODEL_*                                                     */
-    int32_t has_gradient;    /* 0: eval only (hasgradient(model) == false, mcmcmodels.jl:19)      */
+    int32_t has_gradient;    /* 0: eval only (hasgradient(model) == false, mcmcmodels.jl:19); 1: gradient;
+                                2: gradient and metric tensor (hastensor(model), mcmcmodels.jl:20): PROBIT uses
+                                examples/probit_regression.jl:44-49, G = X' diag(v) X + I/prior_sigma^2 with
+                                v = exp(-eta^2 - logcdf(eta) - logcdf(-eta) - log 2 pi); LOGISTIC the expected Fisher
+                                information plus the prior precision, v = p (1 - p) for either link_sign (the metric of
+                                Girolami & Calderhead 2011 for this model; the reference's logistic example passes no
+                                tensor).  Any other kind answers MCMC_E_UNSUPPORTED                     */
     int64_t d;               /* parameter vector size (model.size)                               */
     const double* init;      /* [d]  model.init                                                  */
     const double* scale;     /* [d]  model.scale (NULL -> ones)                                   */
@@ -118,13 +124,13 @@ typedef struct {
 } mcmc_model_desc;
 
 typedef struct {
-    int32_t kind;            /* MCMC_RWM | MCMC_MALA | MCMC_HMC | MCMC_HMCDA | MCMC_RAM | MCMC_NUTS */
+    int32_t kind;            /* MCMC_RWM | MCMC_MALA | MCMC_HMC | MCMC_HMCDA | MCMC_RAM | MCMC_NUTS | MCMC_SMMALA */
     double scale;            /* RWM, RAM: scale (RWM.jl:25, RAM.jl:23)                             */
-    double drift_step;       /* MALA: driftStep (MALA.jl:51)                                       */
+    double drift_step;       /* MALA: driftStep (MALA.jl:51); SMMALA: driftStep (SMMALA.jl:24)     */
     int64_t n_leaps;         /* HMC: nLeaps (HMC.jl:54); NUTS: maxdoublings (NUTS.jl:31)          */
     double leap_step;        /* HMC: leapStep (HMC.jl:55)                                          */
     double rate, len, shrinkage, t0, step;   /* HMCDA (HMCDA.jl:25-29); rate: RAM target rate (RAM.jl:24) */
-    int32_t tuner;           /* 0: nothing; 1: EmpiricalMCMCTuner (MALA, HMC)                      */
+    int32_t tuner;           /* 0: nothing; 1: EmpiricalMCMCTuner (MALA, HMC, SMMALA)              */
     int64_t adapt_step, max_step;            /* EmpMCTuner (samplers.jl:33-37)                      */
     double target_path, target_rate;
     int64_t max_leaps;       /* HMCDA/HMC-tuner safety cap on leapfrogs per step (0 -> 1<<20)      */
@@ -172,6 +178,11 @@ int mcmc_model_destroy(mcmc_model* model);
 /* evaluate log-target (and gradient) of `nchains` parameter vectors x[d][nchains] on the device
  * (model.eval / model.evalallg, likmodel.jl:21,25); host pointers. grad may be NULL. */
 int mcmc_model_eval(mcmc_model* model, int64_t nchains, const double* x, double* lp, double* grad);
+/* model.evalallt (likmodel.jl): log-target, gradient and the metric tensor G of x[d][nchains]; host pointers, lp and
+ * grad may be NULL.  G is symmetric and packed like the RAM factor: element (r, c), c <= r, of chain k at
+ * G[(r(r+1)/2 + c) * nchains + k] (d(d+1)/2 * nchains doubles).  lp and grad are mcmc_model_eval's bit for bit.  A model
+ * created without has_gradient == 2 answers MCMC_E_NEEDS_GRADIENT, "model has no tensor function"; built for d <= 16. */
+int mcmc_model_eval_tensor(mcmc_model* model, int64_t nchains, const double* x, double* lp, double* grad, double* G);
 
 /* ---- sampler config validation (the reference constructors' @asserts) ---- */
 int mcmc_sampler_validate(const mcmc_sampler_cfg* cfg);
@@ -188,7 +199,14 @@ int mcmc_runner_validate(const mcmc_runner_cfg* cfg);
  * models and maxdoublings 11..19 (valid in the reference) answer MCMC_E_UNSUPPORTED; mcmc_run_seqmc refuses NUTS
  * targets (NUTS adapts by its own step counter).  The initial epsilon search (NUTS.jl:71-82) runs here and again at
  * mcmc_chains_reset; mcmc_chains_set_state keeps epsilon and the dual-averaging state (the :reset hook,
- * NUTS.jl:61-63).  The accept bit of a kept NUTS step is 1 if any doubling's candidate was taken. */
+ * NUTS.jl:61-63).  The accept bit of a kept NUTS step is 1 if any doubling's candidate was taken.
+ * SMMALA (SMMALA.jl:39-123): built for PROBIT and LOGISTIC models with a tensor (has_gradient == 2) and d <= 16; a wider d
+ * answers MCMC_E_UNSUPPORTED, a model without a tensor MCMC_E_NEEDS_GRADIENT ("SMMALA sampler requires model with tensor
+ * function", after the gradient check), a start whose log-target is not finite or whose G has a Cholesky pivot <= 0 or
+ * not finite MCMC_E_INIT_OUT_OF_SUPPORT.  Outputs, tuner (EmpiricalMALATune) and tuner_state are MALA's; evals count one
+ * per step plus the initial one.  A proposal out of support, or whose G or h invG fails a pivot, is rejected (the
+ * reference would throw out of chol).  mcmc_chains_set_state keeps invG and firstTerm of the previous position (the
+ * :reset hook as written, SMMALA.jl:54-57); mcmc_run_seqmc refuses SMMALA targets. */
 int mcmc_chains_create(mcmc_model* model, const mcmc_sampler_cfg* sampler, int64_t nchains,
                        int64_t chain_offset, uint64_t seed, const double* init_x, mcmc_chains** out);
 int mcmc_chains_destroy(mcmc_chains* chains);
@@ -207,7 +225,7 @@ int mcmc_chains_fork(mcmc_chains* src, int64_t first, int64_t count, mcmc_chains
 /* steps consumed so far (the sampler's own loop counter i). */
 int mcmc_chains_steps_done(mcmc_chains* chains, int64_t* steps);
 /* per-chain adaptive state after the last run, [nchains] each (any may be NULL): step = the current step size
- * (MALA driftStep under EmpiricalMALATune, HMC leapStep under EmpiricalHMCTune, HMCDA leapStep, HMCDA.jl:136,140);
+ * (MALA / SMMALA driftStep under EmpiricalMALATune, HMC leapStep under EmpiricalHMCTune, HMCDA leapStep, HMCDA.jl:136,140);
  * step_bar = HMCDA's dual-averaged dualLeapStep (HMCDA.jl:138); nleaps = the tuned HMC nLeaps (HMC.jl:42).
  * NUTS: step = epsilon, step_bar = exp(log epsilon_bar) (NUTS.jl:169-172).
  * A quantity the sampler does not adapt reads NaN (steps) or 0 (nleaps). */

@@ -13,7 +13,7 @@ enum DistKind : int32_t {
     DK_NORMAL = 1, DK_UNIFORM = 2, DK_WEIBULL = 3, DK_BETA = 4, DK_TDIST = 5, DK_EXPONENTIAL = 6, DK_GAMMA = 7,
     DK_CAUCHY = 8, DK_LOGNORMAL = 9, DK_LAPLACE = 10
 };
-enum SamplerKind : int32_t { SK_RWM = 1, SK_MALA = 2, SK_HMC = 3, SK_HMCDA = 4, SK_RAM = 5, SK_NUTS = 6 };
+enum SamplerKind : int32_t { SK_RWM = 1, SK_MALA = 2, SK_HMC = 3, SK_HMCDA = 4, SK_RAM = 5, SK_NUTS = 6, SK_SMMALA = 7 };
 
 // Model parameters as the kernels see them (device pointers).
 struct ModelArgs {
@@ -66,6 +66,12 @@ struct ChainState {
     int64_t ram_hs;             // RAM: doubles from the first half of ram_L to the second
     double* nuts_wv;            // NUTS level stack, vectors [maxdoublings][3][d][ld] (nuts.hpp; dead between steps)
     double* nuts_ws;            // NUTS level stack, scalars [maxdoublings][4][ld] (two-lanes-per-chain: [2 ld])
+    double* sm_G;               // SMMALA: metric tensor at x, packed lower rows [d(d+1)/2][ld] (element (r, c) at row
+                                //   r(r+1)/2 + c), its inverse sm_invG likewise, and firstTerm = invG grad [d][ld]
+    double* sm_invG;
+    double* sm_ft;
+    double* sm_pG;              // SMMALA: the proposal's tensor and inverse (dead between steps)
+    double* sm_pinvG;
 };
 
 // One launch of the fused step kernel.

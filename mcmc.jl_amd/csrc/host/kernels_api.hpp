@@ -46,6 +46,13 @@ hipError_t mcmc_launch_glm_record(const mcmc::KernelArgs& a, const mcmc::LeapRec
 hipError_t mcmc_launch_glm_eval(const mcmc::KernelArgs& a, const double* xin, double* lp, double* g, int check,
                                 hipStream_t st);
 int mcmc_glm_max_d();
+// SMMALA on the probit / logistic models, d <= mcmc_smmala_max_d() (smmala.hip), state [d][ld] and packed matrices
+// [d(d+1)/2][ld].  The evaluation alone: lp, gradient g, tensor G, and with invG != NULL its inverse and
+// ft = invG g; check != 0: a non-finite lp or a failed Cholesky pivot sets the error word
+hipError_t mcmc_launch_smmala_eval(const mcmc::KernelArgs& a, const double* xin, double* lp, double* g, double* G,
+                                   double* invG, double* ft, int check, hipStream_t st);
+hipError_t mcmc_launch_smmala_step(const mcmc::KernelArgs& a, hipStream_t st);
+int mcmc_smmala_max_d();
 // RAM on regression targets, 32 < d <= 1024 (glm_ram_wave.hip): per step the eval kernel and the accept / factor-update
 // kernel; u [C][ustride], nz [C], xprop [d][ld], lpp [C] are the device buffers between them.  st2 (may be null):
 // a second stream on which half of a large batch runs, forked from and joined back to st by the two events

@@ -249,6 +249,9 @@ extern "C" int mcmc_sampler_validate(const mcmc_sampler_cfg* s) {
         case MCMC_MALA:
             if (!(s->drift_step > 0)) return fail(MCMC_E_INVALID_ARG, "MALA drift step should be > 0"); // MALA.jl:55
             break;
+        case MCMC_SMMALA:
+            if (!(s->drift_step > 0)) return fail(MCMC_E_INVALID_ARG, "SMMALA drift step should be > 0"); // SMMALA.jl:27
+            break;
         case MCMC_HMC:
             if (!(s->n_leaps > 0)) return fail(MCMC_E_INVALID_ARG, "inner steps should be > 0");        // HMC.jl:60
             if (!(s->leap_step > 0)) return fail(MCMC_E_INVALID_ARG, "inner steps scaling should be > 0"); // HMC.jl:61
@@ -355,6 +358,12 @@ extern "C" int mcmc_model_create(mcmc_ctx* ctx, const mcmc_model_desc* desc, mcm
     m->scale.assign((size_t)d, 1.0);
     if (desc->scale) m->scale.assign(desc->scale, desc->scale + d);
     m->has_gradient = desc->has_gradient;
+    // has_gradient == 2: gradient and metric tensor (hastensor(m), mcmcmodels.jl:20); built for the probit model
+    // (examples/probit_regression.jl:44-49) and the logistic model (expected Fisher information + prior precision)
+    if (desc->has_gradient == 2 && desc->kind != MCMC_MODEL_PROBIT && desc->kind != MCMC_MODEL_LOGISTIC) {
+        delete m;
+        return fail(MCMC_E_UNSUPPORTED, "this model kind has no tensor function (built: PROBIT, LOGISTIC)");
+    }
     ModelArgs& a = m->args;
     a.kind = desc->kind;
     a.d = (int32_t)d;
@@ -633,12 +642,59 @@ extern "C" int mcmc_model_eval(mcmc_model* m, int64_t nchains, const double* x, 
     return rc;
 }
 
+// model.evalallt (likmodel.jl): log-target, gradient and metric tensor of nchains parameter vectors; G packed by rows,
+// element (r, c), c <= r, of chain k at G[(r(r+1)/2 + c) * nchains + k]
+extern "C" int mcmc_model_eval_tensor(mcmc_model* m, int64_t nchains, const double* x, double* lp, double* grad,
+                                      double* G) {
+    if (!m || !x || !G) return fail(MCMC_E_INVALID_ARG, "NULL argument");
+    if (nchains <= 0) return fail(MCMC_E_INVALID_ARG, "nchains should be > 0");
+    if (m->has_gradient != 2) return fail(MCMC_E_NEEDS_GRADIENT, "model has no tensor function");
+    mcmc_ctx* ctx = m->ctx;
+    if (int r = set_device(ctx)) return r;
+    const int d = m->args.d;
+    if (d > mcmc_smmala_max_d())
+        return fail(MCMC_E_UNSUPPORTED, "the tensor is built for d <= " + std::to_string(mcmc_smmala_max_d()));
+    const int64_t ld = round_up(nchains, 64);
+    const size_t nr = (size_t)d * (size_t)(d + 1) / 2;
+    double *dcols = nullptr, *dx = nullptr, *dlp = nullptr, *dg = nullptr, *dG = nullptr;
+    hipStream_t st = ctx->stream;
+    int rc = MCMC_OK;
+    do {
+        if ((rc = dmalloc(&dcols, (size_t)d * nchains))) break;
+        if ((rc = dmalloc(&dx, (size_t)d * ld))) break;
+        if ((rc = dmalloc(&dlp, (size_t)ld))) break;
+        if ((rc = dmalloc(&dg, (size_t)d * ld))) break;
+        if ((rc = dmalloc(&dG, nr * (size_t)ld))) break;
+        hipError_t e = hipMemcpyAsync(dcols, x, (size_t)d * nchains * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = mcmc_copy_cols(dx, ld, dcols, nchains, d, nchains, st);
+        KernelArgs a = base_args(m, nchains, ld);
+        if (e == hipSuccess) e = mcmc_launch_smmala_eval(a, dx, dlp, dg, dG, nullptr, nullptr, 0, st);
+        if (e == hipSuccess && lp) e = hipMemcpyAsync(lp, dlp, (size_t)nchains * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && grad)
+            e = hipMemcpy2DAsync(grad, (size_t)nchains * 8, dg, (size_t)ld * 8, (size_t)nchains * 8, (size_t)d,
+                                 hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipMemcpy2DAsync(G, (size_t)nchains * 8, dG, (size_t)ld * 8, (size_t)nchains * 8, nr,
+                                 hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = fail(MCMC_E_HIP, std::string("model eval tensor: ") + hipGetErrorString(e));
+    } while (0);
+    (void)hipStreamSynchronize(st);
+    dfree(dcols);
+    dfree(dx);
+    dfree(dlp);
+    dfree(dg);
+    dfree(dG);
+    return rc;
+}
+
 // ------------------------------------------------------------------ chains
 static void free_state(mcmc_chains* c) {
     ChainState& s = c->st;
     dfree(s.x); dfree(s.lp); dfree(s.g); dfree(s.t_step); dfree(s.t_bar); dfree(s.t_h);
     dfree(s.t_leaps); dfree(s.t_acc); dfree(s.t_prop); dfree(s.ram_L); dfree(s.mom);
     dfree(s.t_mu); dfree(s.nuts_wv); dfree(s.nuts_ws);
+    dfree(s.sm_G); dfree(s.sm_invG); dfree(s.sm_ft); dfree(s.sm_pG); dfree(s.sm_pinvG);
     s = ChainState{};
 }
 
@@ -650,6 +706,7 @@ static hipError_t launch_chain_step(const mcmc_chains* c, const KernelArgs& a, h
                                         st == ctx->stream ? ctx->stream2 : nullptr, ctx->ev_fork, ctx->ev_join);
     }
     if (c->sa.kind == SK_NUTS) return mcmc_launch_nuts(a, 0, st);
+    if (c->sa.kind == SK_SMMALA) return mcmc_launch_smmala_step(a, st);
     return launch_step(c->layout, a, st);
 }
 
@@ -670,7 +727,7 @@ static void stream_args(const mcmc_chains* c, KernelArgs& a) {
 // one device-scope atomic per wave on a single address serialises at the memory side (32 768 of them per 2^20-chain
 // launch of the pair kernel, ~10 ns apart) and held a short launch's tail for hundreds of microseconds.
 static bool evals_on_host(const mcmc_chains* c) {
-    return c->sa.kind == SK_RWM || c->sa.kind == SK_MALA || c->sa.kind == SK_RAM;
+    return c->sa.kind == SK_RWM || c->sa.kind == SK_MALA || c->sa.kind == SK_RAM || c->sa.kind == SK_SMMALA;
 }
 
 // Regression HMC / HMCDA: the chains' order for the next run, longest trajectory first.  A 16-chain MFMA tile runs
@@ -741,8 +798,14 @@ static int init_state(mcmc_chains* c) {
         HIP_TRY(mcmc_broadcast_cols(c->st.x, c->ld, m->d_init, d, c->C, st));
     }
     KernelArgs a = base_args(m, c->C, c->ld);
-    HIP_TRY(launch_eval(c->layout, a, c->st.x, c->st.lp, c->st.g, 1, st));
-    if (sa.kind == SK_MALA && sa.tuner) HIP_TRY(mcmc_fill_f64(c->st.t_step, c->C, sa.drift_step, st));
+    if (sa.kind == SK_SMMALA) {
+        // evalallt at the start, invG and firstTerm = invG grad (SMMALA.jl:62-67); a failed pivot sets the error word
+        HIP_TRY(mcmc_launch_smmala_eval(a, c->st.x, c->st.lp, c->st.g, c->st.sm_G, c->st.sm_invG, c->st.sm_ft, 1, st));
+        c->h_evals = c->C;
+    } else {
+        HIP_TRY(launch_eval(c->layout, a, c->st.x, c->st.lp, c->st.g, 1, st));
+    }
+    if ((sa.kind == SK_MALA || sa.kind == SK_SMMALA) && sa.tuner) HIP_TRY(mcmc_fill_f64(c->st.t_step, c->C, sa.drift_step, st));
     if (sa.kind == SK_HMC && sa.tuner) {
         HIP_TRY(mcmc_fill_f64(c->st.t_step, c->C, sa.leap_step, st));
         HIP_TRY(mcmc_fill_i32(c->st.t_leaps, c->C, (int32_t)sa.n_leaps, st));
@@ -801,14 +864,21 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
         return fail(MCMC_E_UNSUPPORTED, "RAM is built for d <= " + std::to_string(mcmc_wpc_ram_max_d()) +
                                         " (the d x d jump factor of every chain is kept in HBM)");
     if (s->kind != MCMC_RWM && s->kind != MCMC_RAM && !m->has_gradient) {
-        const char* nm = s->kind == MCMC_MALA ? "MALA" : s->kind == MCMC_HMC ? "HMC" : s->kind == MCMC_NUTS ? "NUTS" : "HMCDA";
+        const char* nm = s->kind == MCMC_MALA ? "MALA" : s->kind == MCMC_HMC ? "HMC" : s->kind == MCMC_NUTS ? "NUTS"
+                         : s->kind == MCMC_SMMALA ? "SMMALA" : "HMCDA";
         return fail(MCMC_E_NEEDS_GRADIENT, std::string(nm) + " sampler requires model with gradient function");
     }
+    if (s->kind == MCMC_SMMALA && m->has_gradient != 2)                                                  // SMMALA.jl:51
+        return fail(MCMC_E_NEEDS_GRADIENT, "SMMALA sampler requires model with tensor function");
     mcmc_ctx* ctx = m->ctx;
     if (int r = set_device(ctx)) return r;
     const int d = m->args.d;
     if (model_is_separable(m) && d > mcmc_wpc_max_d())
         return fail(MCMC_E_UNSUPPORTED, "separable targets support d <= 16384");
+    if (s->kind == MCMC_SMMALA && d > mcmc_smmala_max_d())
+        return fail(MCMC_E_UNSUPPORTED, "SMMALA is built for d <= " + std::to_string(mcmc_smmala_max_d()) +
+                                            " (the metric tensor of a 16-chain tile is held in registers); d = " +
+                                            std::to_string(d));
     if (s->kind == MCMC_NUTS) {
         if (model_is_glm(m))
             return fail(MCMC_E_UNSUPPORTED, "NUTS is not built for the regression models (built: the separable and joint "
@@ -856,7 +926,15 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
     if (c->layout == LAYOUT_GLM && d > 128 && (sa.kind == SK_HMC || sa.kind == SK_HMCDA))   // d-sliced: momentum
         if (int r = dmalloc(&c->st.mom, (size_t)mcmc_glm_d_pad(d) * c->ld)) return bail(r);      // parking (glm_hmc)
     if (int r = dmalloc(&c->st.lp, nc)) return bail(r);
-    const bool tuned = sa.tuner && (sa.kind == SK_MALA || sa.kind == SK_HMC);
+    const bool tuned = sa.tuner && (sa.kind == SK_MALA || sa.kind == SK_HMC || sa.kind == SK_SMMALA);
+    if (sa.kind == SK_SMMALA) {
+        const size_t nr = (size_t)d * (size_t)(d + 1) / 2 * (size_t)c->ld;
+        if (int r = dmalloc(&c->st.sm_G, nr)) return bail(r);
+        if (int r = dmalloc(&c->st.sm_invG, nr)) return bail(r);
+        if (int r = dmalloc(&c->st.sm_pG, nr)) return bail(r);
+        if (int r = dmalloc(&c->st.sm_pinvG, nr)) return bail(r);
+        if (int r = dmalloc(&c->st.sm_ft, nst)) return bail(r);
+    }
     if (tuned || sa.kind == SK_HMCDA || sa.kind == SK_NUTS)
         if (int r = dmalloc(&c->st.t_step, nc)) return bail(r);
     if (sa.kind == SK_NUTS) {
@@ -975,7 +1053,10 @@ extern "C" int mcmc_chains_set_state(mcmc_chains* c, const double* x, double* lp
     hipError_t e = hipMemcpyAsync(dcols, x, (size_t)d * C * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = cols_to_state(c->layout, c->st.x, c->ld, dcols, C, d, C, st);
     KernelArgs a = base_args(m, C, c->ld);
-    if (e == hipSuccess) e = launch_eval(c->layout, a, c->st.x, c->st.lp, c->st.g, 0, st);
+    // SMMALA's :reset hook (SMMALA.jl:54-57) re-evaluates evalallt only: invG and firstTerm stay as they were
+    if (e == hipSuccess && c->sa.kind == SK_SMMALA)
+        e = mcmc_launch_smmala_eval(a, c->st.x, c->st.lp, c->st.g, c->st.sm_G, nullptr, nullptr, 0, st);
+    else if (e == hipSuccess) e = launch_eval(c->layout, a, c->st.x, c->st.lp, c->st.g, 0, st);
     if (e == hipSuccess && lp) e = hipMemcpyAsync(lp, c->st.lp, (size_t)C * 8, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     (void)hipStreamSynchronize(st);
@@ -1033,6 +1114,14 @@ extern "C" int mcmc_chains_fork(mcmc_chains* src, int64_t first, int64_t count, 
     };
     hipError_t e = cols(c->st.x, src->st.x);
     if (e == hipSuccess) e = cols(c->st.g, src->st.g);
+    if (e == hipSuccess) e = cols(c->st.sm_ft, src->st.sm_ft);
+    auto packed = [&](double* dst, const double* from) -> hipError_t {      // SMMALA: [d(d+1)/2][ld]
+        if (!dst || !from) return hipSuccess;
+        return hipMemcpy2DAsync(dst, (size_t)c->ld * 8, from + first, (size_t)src->ld * 8, (size_t)count * 8,
+                                (size_t)d * (size_t)(d + 1) / 2, hipMemcpyDeviceToDevice, st);
+    };
+    if (e == hipSuccess) e = packed(c->st.sm_G, src->st.sm_G);
+    if (e == hipSuccess) e = packed(c->st.sm_invG, src->st.sm_invG);
     if (e == hipSuccess) e = vec(c->st.lp, src->st.lp, 8);
     if (e == hipSuccess) e = vec(c->st.t_step, src->st.t_step, 8);
     if (e == hipSuccess) e = vec(c->st.t_bar, src->st.t_bar, 8);
@@ -1071,6 +1160,7 @@ extern "C" int mcmc_chains_fork(mcmc_chains* src, int64_t first, int64_t count, 
     if (e != hipSuccess) return bail(e);
     HIP_TRY(hipMemsetAsync(c->d_evals, 0, sizeof(unsigned long long), st));   // NUTS: create's epsilon search counted
     HIP_TRY(hipStreamSynchronize(st));
+    c->h_evals = 0;
     c->steps_done = src->steps_done;
     c->spl = src->spl;
     c->store_grads = src->store_grads;
@@ -1561,6 +1651,9 @@ extern "C" int mcmc_run_seqmc(mcmc_chains* const* targets, int32_t ntargets, int
             return fail(MCMC_E_INVALID_ARG, "Models do not have the same parameter vector size");  // SeqMC.jl:49
         if (targets[t]->model->ctx != ctx) return fail(MCMC_E_INVALID_ARG, "targets live on different contexts");
         if (targets[t]->C != npart) return fail(MCMC_E_INVALID_ARG, "every target needs nchains == npart");
+        if (targets[t]->sa.kind == SK_SMMALA)
+            return fail(MCMC_E_UNSUPPORTED, "SeqMC does not run SMMALA targets: the sampler's reset hook keeps invG and "
+                                            "firstTerm of the chain's previous position (SMMALA.jl:54-57)");
         if (targets[t]->sa.kind == SK_NUTS)
             return fail(MCMC_E_UNSUPPORTED, "SeqMC does not run NUTS targets: NUTS adapts epsilon by its own step counter "
                                             "(NUTS.jl:166), which a population runner's resets do not carry");

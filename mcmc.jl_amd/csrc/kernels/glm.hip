@@ -2040,7 +2040,9 @@ static unsigned glm_grid(int64_t C, const GlmShape& g) {
 
 }  // namespace mcmc
 
-#ifdef GLM_MALA1_UNIT
+#if defined(GLM_DEVICE_ONLY)
+// smmala.hip: the device helpers above only
+#elif defined(GLM_MALA1_UNIT)
 #ifdef GLM_WS_STAMP
 extern "C" int mcmc_debug_ws_stamps(unsigned* out) {
     return hipMemcpyFromSymbol(out, HIP_SYMBOL(mcmc::g_ws_stamps), sizeof(mcmc::g_ws_stamps)) == hipSuccess ? 0 : 4;

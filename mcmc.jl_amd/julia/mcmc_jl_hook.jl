@@ -149,6 +149,9 @@ hip_cfg(kind, scale, drift, nl, ls, rate, len, shr, t0, st, tu, maxl) =
 hip_sampler(s::RWM) = (s.tuner == nothing || error("RWM tuners are not built for the GPU");
                        hip_cfg(1, s.scale, 0., 0, 0., 0., 0., 0., 0., 0., hip_tuner(nothing), 0))
 hip_sampler(s::MALA) = hip_cfg(2, 0., s.driftStep, 0, 0., 0., 0., 0., 0., 0., hip_tuner(s.tuner), 0)
+# SMMALA (MCMC_SMMALA = 7): MALA's fields; the library needs a model created with has_gradient = 2 (a tensor function),
+# built for the probit and logistic catalogue models with d <= 16
+hip_sampler(s::SMMALA) = hip_cfg(7, 0., s.driftStep, 0, 0., 0., 0., 0., 0., 0., hip_tuner(s.tuner), 0)
 hip_sampler(s::HMC) = hip_cfg(3, 0., 0., s.nLeaps, s.leapStep, 0., 0., 0., 0., 0., hip_tuner(s.tuner), 0)
 hip_sampler(s::HMCDA) = hip_cfg(4, 0., 0., 0, 0., s.rate, s.len, s.shrinkage, s.t0, s.step, hip_tuner(nothing), 0)
 hip_sampler(s::RAM) = hip_cfg(5, s.scale, 0., 0, 0., s.rate, 0., 0., 0., 0., hip_tuner(nothing), 0)
@@ -363,7 +366,7 @@ function hip_run_group(m::MCMCHipModel, s::MCMCSampler, r::SerialMC, n::Int, see
   end
 end
 
-has_grads(s::MCMCSampler) = isa(s, MALA) || isa(s, HMC) || isa(s, HMCDA) || isa(s, NUTS)
+has_grads(s::MCMCSampler) = isa(s, MALA) || isa(s, SMMALA) || isa(s, HMC) || isa(s, HMCDA) || isa(s, NUTS)
 # the sampler's own diagnostics of kept step j, chain c: {"accept"} for the Metropolis samplers, NUTS's
 # {"epsilon", "ndoublings"} (NUTS.jl:177, which has no "accept")
 function hip_step_diag(s::MCMCSampler, o::HipRun, j::Int, c::Int)

@@ -33,7 +33,7 @@ from ._lib import check, dptr
 __all__ = [
     "IsoNormalDot", "NormalDSL", "AbsNormalDSL", "DistDSL", "DistObsDSL", "LogisticRegression", "LinearRegression", "ProbitRegression", "vaso_data",
     "OrnsteinUhlenbeck", "ou_series", "MCMCLikelihoodModel", "model",
-    "RWM", "MALA", "HMC", "HMCDA", "RAM", "NUTS", "EmpMCTuner", "EmpiricalMCMCTuner", "SerialMC", "MCMCTask", "MCMCChain",
+    "RWM", "MALA", "SMMALA", "HMC", "HMCDA", "RAM", "NUTS", "EmpMCTuner", "EmpiricalMCMCTuner", "SerialMC", "MCMCTask", "MCMCChain",
     "run", "resume", "device_count",
 ]
 
@@ -193,7 +193,8 @@ def vaso_data(path):
 class MCMCLikelihoodModel:
     """MCMCLikelihoodModel (likmodel.jl:20-57): target + init + scale + pmap, uploaded once per GPU."""
 
-    def __init__(self, target, init, scale=1.0, gradient: bool = False, pmap: Optional[dict] = None):
+    def __init__(self, target, init, scale=1.0, gradient: bool = False, pmap: Optional[dict] = None,
+                 tensor: bool = False):
         self.target = target
         init = [float(init)] if np.isscalar(init) else init                   # likmodel.jl:112
         self.init = _f64(init).reshape(-1)
@@ -206,6 +207,9 @@ class MCMCLikelihoodModel:
             raise AssertionError(f"scale parameter size ({self.scale.shape[0]}) different from initial values "
                                  f"({self.size})")
         self.has_gradient = bool(gradient)         # hasgradient(m) = m.evalg != nothing (mcmcmodels.jl:19)
+        self.has_tensor = bool(tensor)             # hastensor(m) = m.evalt != nothing (mcmcmodels.jl:20)
+        if self.has_tensor and not self.has_gradient:
+            raise AssertionError("a model with a tensor function needs its gradient function (gradient=True)")
         self.pmap = pmap if pmap is not None else {"pars": (1, (self.size,))}  # likmodel.jl:118
         if hasattr(target, "X"):
             if target.X.ndim != 2 or target.X.shape[1] != self.size:
@@ -229,7 +233,7 @@ class MCMCLikelihoodModel:
         t = self.target
         desc = _lib.ModelDesc()
         desc.kind = t.kind
-        desc.has_gradient = 1 if self.has_gradient else 0
+        desc.has_gradient = 2 if self.has_tensor else 1 if self.has_gradient else 0
         desc.d = self.size
         desc.init = dptr(self.init)
         desc.scale = dptr(self.scale)
@@ -265,6 +269,23 @@ class MCMCLikelihoodModel:
             return lp[0], (g[:, 0] if g is not None else None)
         return lp, g
 
+    def evalallt(self, x, device: int = 0):
+        """model.evalallt on a batch: x [d] or [d, nchains] -> (lp, grad, G), G [d, d] or [d, d, nchains]: the metric
+        tensor (probit: examples/probit_regression.jl:44-49; logistic: expected Fisher information + prior precision)."""
+        xa = np.asarray(x, dtype=np.float64)
+        single = xa.ndim == 1
+        xa = np.ascontiguousarray(xa.reshape(self.size, -1))
+        C, d = xa.shape[1], self.size
+        lp, g, Gp = np.empty(C), np.empty((d, C)), np.empty((d * (d + 1) // 2, C))
+        check(_lib.load().mcmc_model_eval_tensor(self._handle(device), C, dptr(xa), dptr(lp), dptr(g), dptr(Gp)))
+        G = np.empty((d, d, C))
+        for r in range(d):
+            for c in range(r + 1):
+                G[r, c] = G[c, r] = Gp[r * (r + 1) // 2 + c]
+        if single:
+            return lp[0], g[:, 0], G[:, :, 0]
+        return lp, g, G
+
     def __mul__(self, sampler):
         return _ModelSampler(self, sampler)
 
@@ -278,7 +299,7 @@ class MCMCLikelihoodModel:
 
 
 def model(f, mtype: str = "likelihood", init=None, scale=1.0, gradient: bool = False,
-          grad=None, **dsl_init) -> MCMCLikelihoodModel:
+          grad=None, tensor: bool = False, **dsl_init) -> MCMCLikelihoodModel:
     """model() entry point (mcmcmodels.jl:27-33).
 
     Function style (likmodel.jl:100-143): model(IsoNormalDot(), init=ones(3)) has no gradient, like
@@ -296,7 +317,9 @@ def model(f, mtype: str = "likelihood", init=None, scale=1.0, gradient: bool = F
         init = [1.0]                                                                       # likmodel.jl:107
     if grad is not None and grad is not False:
         gradient = True
-    return MCMCLikelihoodModel(f, init, scale=scale, gradient=gradient)
+    # tensor=True: the model's metric tensor (model(...; tensor=...), examples/probit_regression.jl:69); built for
+    # ProbitRegression and LogisticRegression
+    return MCMCLikelihoodModel(f, init, scale=scale, gradient=gradient, tensor=bool(tensor))
 
 
 # ------------------------------------------------------------------ samplers
@@ -372,6 +395,21 @@ class MALA(_Sampler):
         c = super().cfg()
         c.drift_step = self.driftStep
         return c
+
+
+class SMMALA(MALA):
+    """Simplified manifold MALA (SMMALA.jl:20-37): MALA's constructor forms; needs a model with a tensor function."""
+    kind = _lib.SAMPLER_SMMALA
+    uses_tensor = True
+
+    def __init__(self, driftStep: Union[float, EmpiricalMCMCTuner] = 1.0, tuner=None, scale: Optional[float] = None):
+        if isinstance(driftStep, EmpiricalMCMCTuner):
+            driftStep, tuner = 1.0, driftStep
+        if scale is not None:
+            driftStep = scale
+        if not driftStep > 0:
+            raise AssertionError("SMMALA drift step should be > 0")            # SMMALA.jl:27
+        self.driftStep, self.tuner = float(driftStep), tuner
 
 
 class HMC(_Sampler):
@@ -618,6 +656,8 @@ class MCMCTask:
         if sampler.uses_gradient and not model.has_gradient:
             name = type(sampler).__name__
             raise AssertionError(f"{name} sampler requires model with gradient function")
+        if getattr(sampler, "uses_tensor", False) and not getattr(model, "has_tensor", False):           # SMMALA.jl:51
+            raise AssertionError(f"{type(sampler).__name__} sampler requires model with tensor function")
         self.model, self.sampler, self.runner = model, sampler, runner
         self.nchains, self.device = int(nchains), int(device)
         self.seed = None if seed is None else int(seed)
