@@ -92,7 +92,10 @@ __global__ void k_seqmc_resample(int64_t N, int d, const double* cp, const int32
     if (*flag) {
         const u32x4 w = philox4x32_10((uint32_t)n, step, target, TAG_RESAMPLE, key0, key1);
         const double u = uniform52(w.x, w.y);
-        int64_t lo = 0, hi = N - 1;                  // cp[N-1] == 1 > u: the search always succeeds
+        // hi = N - 1 bounds the search whatever cp holds: no index past it is ever read or returned.  cp[N-1] need
+        // not be 1 (pre and total are summed in different associations once N > 256; cp is NaN when every weight
+        // is 0 or one is NaN); a u above every cp[p], or a NaN cp, selects the last particle.
+        int64_t lo = 0, hi = N - 1;
         while (lo < hi) {
             const int64_t mid = lo + (hi - lo) / 2;
             if (cp[mid] >= u) hi = mid;
