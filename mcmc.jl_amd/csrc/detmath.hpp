@@ -327,20 +327,22 @@ __device__ __forceinline__ double bm_radius_u32(uint32_t w, RadTab rt) {
     const uint64_t b = d2bits(y);
     const uint32_t yh = (uint32_t)(b >> 32);
     const bool tail = v < (1u << 21);
-    // byte offset of row (yh >> 15) - ((1023 + 21) << 5) + side * NROWS/2 (yh >> 15 = biased exponent, k)
-    constexpr uint32_t kOff0 = 0u - ((uint32_t)((1023 + 21) << 5) << 4);
-    constexpr uint32_t kOff1 = kOff0 + (uint32_t)(BM_RADP_NROWS / 2) * 16u;
-    // the side select as one v_bfi_b32, the offset as one v_lshl_add_u32 and the residual's high word as one
-    // v_and_or_b32: the compiler spends two instructions on each (VOP3 takes no literal on gfx9)
-    uint32_t sel;
-    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(sel) : "v"(sm), "v"(kOff1), "s"(kOff0));
+    // byte offset of row (yh >> 15) - ((1023 + 21) << 5) + side * NROWS/2 (yh >> 15 = biased exponent, k), biased by
+    // kRowBias: the low 9 bits r9 of yh >> 15 run over [0x80, 0x1c0) in the main range, so the offset is
+    // 16 r9 + (side ? 16 NROWS/2 : 0) - kRowBias -- a v_bfe_u32, a v_and_b32 with a literal and one v_lshl_add_u32,
+    // the constant bias folded into the loads' immediate offsets where the table's address allows (BmLds).  The
+    // residual's high word takes exponent 0x400 from the inline constant 2.0 (one v_and_or_b32): m2 = 2 m, and
+    // t = fma(m2, 0.5, -(1 + 1/64)) is m - (1 + 1/64) exactly (Sterbenz; the halving is exact).  No constant of
+    // either step lives in a VGPR (VOP3 takes no literal on gfx9; round 3's v_bfi_b32 form held two across the loop).
+    constexpr uint32_t kRowBias = (uint32_t)(((1023 + 21) << 5) & 0x1ff) * 16u;
+    const uint32_t sel = sm & ((uint32_t)(BM_RADP_NROWS / 2) * 16u);
     uint32_t off;
-    asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(off) : "v"(yh >> 15), "v"(sel));   // ((yh >> 15) << 4) + sel
+    asm("v_lshl_add_u32 %0, %1, 4, %2" : "=v"(off) : "v"((yh >> 15) & 0x1ffu), "v"(sel));   // 16 r9 + sel
     uint32_t th = yh;                                                   // in place: y's high word is dead now
-    asm("v_and_or_b32 %0, %0, %1, %2" : "+v"(th) : "s"(0x7fffu), "v"(0x3ff00000u));
-    if (!rt.lds) off = tail ? 0u : off;
-    double t = bits2d(((uint64_t)th << 32) | (b & 0xffffffffull)) - (1.0 + 1.0 / 64.0);     // exact (Sterbenz)
-    const char* base = reinterpret_cast<const char*>(rt.d) + off;
+    asm("v_and_or_b32 %0, %0, %1, 2.0" : "+v"(th) : "s"(0x7fffu));     // (yh & 0x7fff) | 0x40000000
+    if (!rt.lds) off = tail ? kRowBias : off;
+    double m2 = bits2d(((uint64_t)th << 32) | (b & 0xffffffffull));
+    const char* base = reinterpret_cast<const char*>(rt.d) + off - kRowBias;
     f64x2_t c0 = *reinterpret_cast<const f64x2_t*>(base);
     f64x2_t c1 = *reinterpret_cast<const f64x2_t*>(base + 16 * BM_RADP_NROWS);
     f64x2_t c2 = *reinterpret_cast<const f64x2_t*>(base + 32 * BM_RADP_NROWS);
@@ -357,7 +359,7 @@ __device__ __forceinline__ double bm_radius_u32(uint32_t w, RadTab rt) {
         const uint64_t bx = d2bits(x);
         const uint32_t xh = (uint32_t)(bx >> 32);
         const uint32_t rw = (uint32_t)((int)(xh >> 15) - ((1023 - 1) << 5)) * 16u + (sm & (16u * (BM_RADT_NROWS / 2)));
-        t = bits2d(((uint64_t)((xh & 0x7fffu) | 0x3ff00000u) << 32) | (bx & 0xffffffffull)) - (1.0 + 1.0 / 64.0);
+        m2 = bits2d(((uint64_t)((xh & 0x7fffu) | 0x40000000u) << 32) | (bx & 0xffffffffull));
         asm volatile(
             "global_load_dwordx4 %0, %4, %5\n\t"
             "global_load_dwordx4 %1, %4, %6\n\t"
@@ -369,6 +371,10 @@ __device__ __forceinline__ double bm_radius_u32(uint32_t w, RadTab rt) {
               "s"(&kBmRadTTab[2 * BM_RADT_NROWS][0]), "s"(&kBmRadTTab[3 * BM_RADT_NROWS][0])
             : "memory");
     }
+    // fma(m2, 0.5, -(1 + 1/64)), exact; written out so that the addend is a scalar operand (the compiler holds it in
+    // a VGPR pair across the caller's loop)
+    double t;
+    asm("v_fma_f64 %0, %1, 0.5, %2" : "=v"(t) : "v"(m2), "s"(-(1.0 + 1.0 / 64.0)));
     double q = __builtin_fma(c3.y, t, c3.x);
     q = __builtin_fma(q, t, c2.y);
     q = __builtin_fma(q, t, c2.x);
@@ -578,8 +584,23 @@ static __device__ const double kBmSinCos1024Tab[1024][2] = {BM_SINCOS1024_TABLE_
 constexpr double kSinJ1 = 0x1.921fb54442d18p-30, kSinJ3 = -0x1.4abbce625be53p-91, kSinJ5 = 0x1.466bc6775aae2p-154;
 constexpr double kCosJ2 = -0x1.3bd3cc9be45dep-60, kCosJ4 = 0x1.03c1f081b5ac4p-122;
 
+// The addends of the two innermost Horner steps, fma(j2, kSinJ5, kSinJ3) and fma(j2, kCosJ4, kCosJ2).  Each step has
+// two constants that are not inline ones and VOP3 reads one scalar operand on gfx9, so the addend has to be in a VGPR
+// pair: as plain constants (the default) the compiler moves them there again for every pair of angles; a step loop
+// with four VGPRs to spare holds them across its steps instead (resident(): the empty asm makes them loop-carried
+// values the compiler can neither fold nor rematerialise).  The same two doubles either way.
+struct AngleK {
+    double s3 = kSinJ3, c2 = kCosJ2;
+    __device__ __forceinline__ static AngleK resident() {
+        AngleK k;
+        asm volatile("" : "+v"(k.s3), "+v"(k.c2));
+        return k;
+    }
+};
+
 __device__ __forceinline__ void det_sincos2pi_u32(uint32_t w, double& s_out, double& c_out,
-                                                  const double (*sct)[2] = kBmSinCos1024Tab) {
+                                                  const double (*sct)[2] = kBmSinCos1024Tab,
+                                                  const AngleK& ak = AngleK{}) {
     // j = the sign-extended low 22 bits of w (w - 2^22 k), one v_bfe_i32, exact in a double, and so is j^2; the
     // polynomials are in j with 2 pi 2^-32 folded into their coefficients: sin r = j (A1 + j^2 (A3 + j^2 A5)),
     // cos r = 1 + j^2 (B2 + j^2 B4), r = 2 pi j 2^-32, |r| <= 2 pi 2^-11.  The row's byte offset 16 k is
@@ -588,8 +609,8 @@ __device__ __forceinline__ void det_sincos2pi_u32(uint32_t w, double& s_out, dou
     const uint32_t off = (w - (uint32_t)ji) >> 18;                     // 16 k
     const double j = (double)ji;
     const double j2 = j * j;
-    const double sr = j * __builtin_fma(j2, __builtin_fma(j2, kSinJ5, kSinJ3), kSinJ1);
-    const double cr = __builtin_fma(j2, __builtin_fma(j2, kCosJ4, kCosJ2), 1.0);
+    const double sr = j * __builtin_fma(j2, __builtin_fma(j2, kSinJ5, ak.s3), kSinJ1);
+    const double cr = __builtin_fma(j2, __builtin_fma(j2, kCosJ4, ak.c2), 1.0);
     typedef double f64x2_t __attribute__((ext_vector_type(2)));
     const f64x2_t a = *reinterpret_cast<const f64x2_t*>(reinterpret_cast<const char*>(sct) + off);   // (sin a, cos a)
     s_out = __builtin_fma(a.x, cr, a.y * sr);
@@ -619,27 +640,32 @@ __device__ __forceinline__ double sqrt_pos_normal(double x) {
 // rt, sct: the radius polynomial (bm_radius_u32) and angle tables, in global memory (default) or a kernel's LDS copies
 __device__ __forceinline__ void normals4(const u32x4& w, double& z0, double& z1, double& z2, double& z3,
                                          RadTab rt = rad_tab_global(),
-                                         const double (*sct)[2] = kBmSinCos1024Tab) {
+                                         const double (*sct)[2] = kBmSinCos1024Tab, const AngleK& ak = AngleK{}) {
     {
         const double rad = bm_radius_u32(w.x, rt);
         double s, c;
-        det_sincos2pi_u32(w.y, s, c, sct);
+        det_sincos2pi_u32(w.y, s, c, sct, ak);
         z0 = rad * c; z1 = rad * s;
     }
     {
         const double rad = bm_radius_u32(w.z, rt);
         double s, c;
-        det_sincos2pi_u32(w.w, s, c, sct);
+        det_sincos2pi_u32(w.w, s, c, sct, ak);
         z2 = rad * c; z3 = rad * s;
     }
     asm volatile("" : "+v"(z0), "+v"(z1), "+v"(z2), "+v"(z3));   // likewise the products
 }
 
 // ratio > det_log(u), exactly (the RWM / MALA test `ratio > log(rand())`, RWM.jl:63, MALA.jl:108).  A
-// single-precision log2 (v_log_f32) decides it when ratio is not within E = 2^-16 (1 + |L|) of L = log2f(u) ln2:
-// |L - log u| <= ln2 (2^-23 |log2 u| + 2^-24 log2 e) plus the 1-ulp error of det_log is hundreds of times smaller
-// than E, so a decided test agrees with the exact one.  The rest (probability ~1e-5 per test; u = 0; NaN ratios)
-// takes det_log, on the lanes that need it.
+// single-precision log2 (v_log_f32) decides it: with L = RN(log2f((float)u) ln2), d = RN(ratio - L) and
+// E = fma(|L|, 2^-16, 2^-16), the lane is decided iff |d| > E, and then accepts iff d > 0.  Soundness: d has the
+// sign of ratio - L (rounding keeps the sign of a non-zero difference) and |ratio - L| >= |d| / (1 + 2^-53) >
+// E (1 - 2^-53) >= 2^-16 (1 + |L|) (1 - 2^-52), the fma being one rounding of 2^-16 (1 + |L|).  Against that,
+// |L - det_log(u)| <= ln2 (2^-23 |log2 u| + 2^-24 log2 e) (v_log_f32 within 1 ulp; u rounded to a float) + 2^-53 |L|
+// (the product's rounding) + the 1-ulp error of det_log < 2^-22 (1 + |L|), 60 times smaller: so ratio - det_log(u)
+// has the sign of ratio - L and is not zero, and a decided test agrees with the exact one.  The rest (probability
+// ~1e-5 per test; u = 0, where L = -inf makes d and E infinite or d a NaN; NaN ratios) takes det_log, on the lanes
+// that need it.  ratio = -inf against a finite L is decided, and rejected.
 // The undecided lanes' exact test, out of line: inlined, its det_log polynomial constants were hoisted out of the
 // step loops into VGPRs and spilled (the metric kernel lpp_rwm<4, true, IsoDot, true> stored 64 B a lane to scratch
 // per launch, ~134 MB at 2^21 lanes, to reload them on this 1-in-10^5 path).  A call saves the caller's live
@@ -647,11 +673,10 @@ __device__ __forceinline__ void normals4(const u32x4& w, double& z0, double& z1,
 __device__ __attribute__((noinline)) bool gt_det_log_exact(double ratio, double u) { return ratio > det_log(u); }
 __device__ __forceinline__ bool gt_det_log(double ratio, double u) {
     const double L = (double)__builtin_amdgcn_logf((float)u) * 0x1.62e42fefa39efp-1;
-    const double E = 0x1p-16 * (1.0 + __builtin_fabs(L));
-    const bool sure_acc = ratio > L + E;
-    const bool sure_rej = ratio <= L - E;
-    bool acc = sure_acc;
-    if (!sure_acc && !sure_rej) acc = gt_det_log_exact(ratio, u);
+    const double d = ratio - L;
+    const double E = __builtin_fma(__builtin_fabs(L), 0x1p-16, 0x1p-16);
+    bool acc = d > 0.0;
+    if (!(__builtin_fabs(d) > E)) acc = gt_det_log_exact(ratio, u);
     return acc;
 }
 

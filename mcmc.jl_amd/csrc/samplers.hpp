@@ -43,11 +43,16 @@ struct BmLds {
     double (*rd)[2];
     double (*sc)[2];
 };
-// The block's LDS copies (one allocation per kernel, whoever asks)
+// The block's LDS copies (one allocation per kernel, whoever asks).  One object with the angle table first: the
+// radius table then starts 16 KB into it, and bm_radius_u32's constant row bias (-2 KB) folds with the table's
+// address and the chunk offsets into the immediate offsets of its ds_read_b128 (an unsigned 16-bit field).
 __device__ __forceinline__ BmLds bm_lds_tables() {
-    __shared__ __attribute__((aligned(16))) double lds_radd[4 * BM_RADP_NROWS][2];
-    __shared__ __attribute__((aligned(16))) double lds_sct[1024][2];
-    return BmLds{lds_radd, lds_sct};
+    struct Tables {
+        double sct[1024][2];
+        double radd[4 * BM_RADP_NROWS][2];
+    };
+    __shared__ __attribute__((aligned(16))) Tables lds_bm;
+    return BmLds{lds_bm.radd, lds_bm.sct};
 }
 
 // The tables into a block's LDS by its NT threads: every 16-byte load of a batch in flight before its first store
@@ -242,26 +247,29 @@ struct PairChain {
         const uint32_t t = tid_now();
         return (int64_t)blockIdx.x * kChainsPerBlock + (int64_t)((t >> 6) * 32 + (t & 31));
     }
+    // the half likewise, for the stores after the step loop (h itself would stay in a VGPR across it)
+    __device__ __forceinline__ static int h_now() { return (int)((tid_now() >> 5) & 1); }
     __device__ __forceinline__ int coord(int k) const { return h * NC + k; }
     __device__ __forceinline__ bool valid(int k) const { return FULL || coord(k) < d; }
     __device__ __forceinline__ uint32_t block(int b) const { return (uint32_t)(h * NB + b); }
-    // half `which`'s value of v in both lanes of the chain (v_permlane32_swap: {half 0's, half 1's} broadcasts)
-    __device__ __forceinline__ double from_half(double v, int which) const {
-        const uint64_t u = (uint64_t)__double_as_longlong(v);
-        const uint32_t lo = (uint32_t)u, hi = (uint32_t)(u >> 32);
-        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
-        const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        return which == 0 ? __longlong_as_double((long long)(((uint64_t)b[0] << 32) | a[0]))
-                          : __longlong_as_double((long long)(((uint64_t)b[1] << 32) | a[1]));
+    // half 0's and half 1's value of v, each in both lanes of the chain: one v_permlane32_swap per dword exchanges
+    // the upper half of one copy of v with the lower half of another, which leaves {half 0's, half 1's}.  The swap
+    // works in place on two registers, so v is needed twice: the second copy is made here as a double (one
+    // v_mov_b64; copying the dwords at the swaps takes a v_mov_b32 each) and hidden from the compiler, which would
+    // otherwise see one value used twice and copy it again.
+    __device__ __forceinline__ void halves(double v, double& v0, double& v1) const {
+        double w = v;
+        asm("" : "+v"(w));
+        const uint64_t u = (uint64_t)__double_as_longlong(v), uw = (uint64_t)__double_as_longlong(w);
+        const auto a = __builtin_amdgcn_permlane32_swap((uint32_t)u, (uint32_t)uw, false, false);
+        const auto b = __builtin_amdgcn_permlane32_swap((uint32_t)(u >> 32), (uint32_t)(uw >> 32), false, false);
+        v0 = __longlong_as_double((long long)(((uint64_t)b[0] << 32) | a[0]));
+        v1 = __longlong_as_double((long long)(((uint64_t)b[1] << 32) | a[1]));
     }
     // (half 0's value) + (half 1's value) in both lanes of the chain, bitwise the same
     __device__ __forceinline__ double reduce(double v) const {
-        const uint64_t u = (uint64_t)__double_as_longlong(v);
-        const uint32_t lo = (uint32_t)u, hi = (uint32_t)(u >> 32);
-        const auto a = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);   // {half 0's, half 1's}
-        const auto b = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
-        const double v0 = __longlong_as_double((long long)(((uint64_t)b[0] << 32) | a[0]));
-        const double v1 = __longlong_as_double((long long)(((uint64_t)b[1] << 32) | a[1]));
+        double v0, v1;
+        halves(v, v0, v1);
         return v0 + v1;
     }
     __device__ __forceinline__ bool any(bool v) const {
@@ -280,8 +288,7 @@ struct PairChain {
     }
     __device__ __forceinline__ void store(double* x, int64_t ld, const double (&v)[NC]) const {
         if (!live) return;
-        const int hn = (int)((tid_now() >> 5) & 1);
-        uint64_t o = (uint64_t)c_now() + (uint64_t)(hn * NC) * (uint64_t)ld;
+        uint64_t o = (uint64_t)c_now() + (uint64_t)(h_now() * NC) * (uint64_t)ld;
 #pragma unroll
         for (int k = 0; k < NC; ++k) {
             if (valid(k)) x[o] = v[k];
@@ -294,7 +301,7 @@ struct PairChain {
     __device__ __forceinline__ T load_t(const T* p) const { return p[live ? c : 0]; }
     template <class T>
     __device__ __forceinline__ void store_t(T* p, T v) const {
-        if (live && h == 0) p[c_now()] = v;
+        if (live && h_now() == 0) p[c_now()] = v;
     }
     __device__ __forceinline__ void store_kept(const StepArgs& s, int64_t kk, const double (&v)[NC],
                                                double* base) const {
@@ -316,7 +323,7 @@ struct PairChain {
     }
     __device__ __forceinline__ void count_evals(const StepArgs& s, int64_t n) const {
         if (s.n_evals == nullptr) return;
-        unsigned long long v = (live && h == 0) ? (unsigned long long)n : 0ull;
+        unsigned long long v = (live && h_now() == 0) ? (unsigned long long)n : 0ull;
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
         if ((threadIdx.x & 63) == 0) atomicAdd(s.n_evals, v);
@@ -454,11 +461,11 @@ struct WaveChain {
 // ------------------------------------------------------------------ shared pieces
 template <class P>
 __device__ __forceinline__ void gen_normals(const P& p, const Stream& rs, uint32_t chain, uint32_t step,
-                                            double (&z)[P::NC]) {
+                                            double (&z)[P::NC], const AngleK& ak = AngleK{}) {
 #pragma unroll
     for (int b = 0; b < P::NB; ++b) {
         const u32x4 w = rs.block_us(chain, step, p.block(b), TAG_NORMAL);
-        normals4(w, z[4 * b], z[4 * b + 1], z[4 * b + 2], z[4 * b + 3], p.bt.rad, p.bt.sct);
+        normals4(w, z[4 * b], z[4 * b + 1], z[4 * b + 2], z[4 * b + 3], p.bt.rad, p.bt.sct, ak);
     }
 }
 
@@ -533,8 +540,11 @@ __device__ __forceinline__ bool mh_accept_short_circuit(const Stream& rs, uint32
 
 // The RWM / MALA test of step i (launch step t), RWM.jl:63 / MALA.jl:108.  PairChain: both lanes of a chain need
 // the same uniform, so on even t the two halves draw steps i (half 0) and i + 1 (half 1) from the counter-based
-// stream at once; half 0's draw is broadcast now and half 1's kept for step t + 1 -- one Philox block per chain per
-// two steps, the same values as mh_accept_short_circuit's conditional draw (the stream is keyed by (chain, step)).
+// stream at once; the swap that broadcasts half 0's draw returns half 1's, broadcast too, as its other result, which
+// is kept for step t + 1: one Philox block and one swap pair per chain per two steps, the same values as
+// mh_accept_short_circuit's conditional draw (the stream is keyed by (chain, step)).  t counts from the launch's
+// first step, so every launch starts on a drawing step whatever its step_begin, and nothing is carried between
+// launches; a launch of odd length draws its last step's pair and drops the second uniform.
 template <class P>
 struct AcceptDraw {
     double u_next = 0.0;
@@ -543,11 +553,9 @@ struct AcceptDraw {
             double u;
             if ((t & 1) == 0) {
                 const u32x4 w = rs.block(chain, (uint32_t)(i + p.h), 0u, TAG_ACCEPT);
-                const double uu = uniform52(w.x, w.y);
-                u = p.from_half(uu, 0);
-                u_next = uu;
+                p.halves(uniform52(w.x, w.y), u, u_next);
             } else {
-                u = p.from_half(u_next, 1);
+                u = u_next;
             }
             bool acc = ratio > 0.0;
             if (!acc) acc = gt_det_log(ratio, u);
@@ -612,12 +620,14 @@ __device__ __forceinline__ void rwm_body(const KernelArgs& a) {
 #pragma unroll
     for (int k = 0; k < P::NC; ++k) sc[k] = p.valid(k) ? (US ? s.scale1 : s.scale[p.coord(k)]) : 0.0;
     AcceptDraw<P> ad;
+    // the pair kernels keep the angle polynomials' two VGPR constants across the step loop (detmath.hpp AngleK)
+    const AngleK ak = P::kPairs ? AngleK::resident() : AngleK{};
 
     Keeper keep(s);
     for (int t = 0; t < s.nsteps; ++t) {
         const int64_t i = s.step_begin + t;
         double xp[P::NC];
-        gen_normals(p, rs, chain, (uint32_t)i, xp);             // xp <- z
+        gen_normals(p, rs, chain, (uint32_t)i, xp, ak);         // xp <- z
 #pragma unroll
         for (int k = 0; k < P::NC; ++k) xp[k] = x[k] + xp[k] * sc[k];   // pars + randn(d) .* scale
         bool oos;
