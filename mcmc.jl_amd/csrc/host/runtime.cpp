@@ -758,13 +758,9 @@ static int glm_trajectory_order(mcmc_chains* c, hipStream_t st) {
     });
     // two tiles a workgroup (d-sliced, 128 < d <= 512): the longest tile shares its workgroup with the shortest, the
     // second longest with the second shortest, ...: the workgroup runs its longer tile's trajectory, and once the
-    // shorter tile's chains have all finished it stops computing (glm_hmc, GLM_TILE_SKIP), so the long tiles -- the
+    // shorter tile's chains have all finished it stops computing (glm_hmc's tile skip), so the long tiles -- the
     // dispatch's end -- run their tails with the SIMDs to themselves.  Whole 32-chain workgroups only.
-    static const bool pair_off = [] {                  // MCMCHIP_TILE_PAIR=0: sorted neighbours share (A/B)
-        const char* e = std::getenv("MCMCHIP_TILE_PAIR");
-        return e != nullptr && e[0] == '0';
-    }();
-    if (!pair_off && mcmc_glm_tiles_per_wg(c->model->args.d) == 2 && C % 32 == 0) {
+    if (mcmc_glm_tiles_per_wg(c->model->args.d) == 2 && C % 32 == 0) {
         const int64_t nt = C / 16;
         std::vector<int32_t> paired((size_t)C);
         for (int64_t w = 0; w < nt / 2; ++w)
@@ -1467,11 +1463,7 @@ int mcmc_run_serialmc_ld(mcmc_chains* c, const mcmc_runner_cfg* r, mcmc_outputs*
     c->last_order = false;
     // regression tiles run their leapfrog loop to their longest chain.  (The lane / pair layouts were measured
     // with the same order and it did not pay: DESIGN.md §5.3.)
-    static const bool order_off = [] {                 // MCMCHIP_TRAJ_ORDER=0: identity order (A/B measurements)
-        const char* e = std::getenv("MCMCHIP_TRAJ_ORDER");
-        return e != nullptr && e[0] == '0';
-    }();
-    if (!order_off && L == LAYOUT_GLM && C > 16 && (c->sa.kind == SK_HMCDA || (c->sa.kind == SK_HMC && c->sa.tuner))) {
+    if (L == LAYOUT_GLM && C > 16 && (c->sa.kind == SK_HMCDA || (c->sa.kind == SK_HMC && c->sa.tuner))) {
         if (int rc = glm_trajectory_order(c, st)) return rc;
         s.order = (const int32_t*)c->order_buf.p;
         c->last_order = true;

@@ -1,7 +1,7 @@
 // smmala.hip -- the metric tensor of the probit / logistic regression models on fp64 MFMA (`evalallt`,
 // likmodel.jl) and the simplified manifold MALA sampler on top of it (src/samplers/SMMALA.jl:39-123), d <= 16.
 //
-// Geometry: the regression family's single-slice one (glm.hip, GlmShape with NM = 1): a wave owns a tile of 16
+// Geometry: the regression family's single-slice one (glm_device.hpp, GlmShape with NM = 1): a wave owns a tile of 16
 // chains, lane (q, cl) chain cl and coordinates 4q + e; four tiles a workgroup share the staged X tiles
 // (glm_layout.hpp image).  The log-target and the gradient are glm_eval1's, operation for operation (eta chains over
 // (e, q); the gradient chains over observations; a lane's likelihood terms in (t, r) order), so they are
@@ -20,10 +20,7 @@
 // Cholesky factor in place (pivots formed by all four lanes, a column's rows by their owners 4q + e), the inverse
 // column by column (lane q owns columns 4q + e: forward then backward substitution in a private LDS vector), the
 // matvecs and quadratic forms by rows.  tests/smmala_oracle.c restates every sum in the same order.
-#define GLM_DEVICE_ONLY 1
-#include "glm.hip"
-
-mcmc::GlmShape mcmc_glm_shape(int d, int64_t n);           // glm.hip
+#include "glm_device.hpp"
 
 namespace mcmc {
 

@@ -1,9 +1,11 @@
 #!/usr/bin/env python3
-"""Phase timing of the d-sliced regression tile loop (dev tool; a GLM_STAMP build, glm.hip GLM_STAMPT).
+"""Phase timing of the d-sliced regression tile loop (dev tool; a GLM_STAMP build of glm.hip: glm_stamps.hpp
+GLM_STAMPT, its sites in glm_device.hpp glm_eval).
 
-Build:  make -C mcmc.jl_amd OBJDIR=build_stamp OUT=mcmchip/libmcmc_hip_stamp.so \
-            FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -DGLM_STAMP"
-Run:    MCMCHIP_LIB=mcmc.jl_amd/mcmchip/libmcmc_hip_stamp.so python3 scripts/glm_stamps.py [d] [n] [chains]
+Build:  hipcc ... -mllvm -disable-machine-licm -mllvm -amdgpu-mfma-vgpr-form -DGLM_STAMP -c csrc/kernels/glm.hip -o build_ab/glm_stamp.o
+        (glm.o's Makefile flags plus -DGLM_STAMP, that unit only) and link it with the other objects into
+        mcmchip/libmcmc_hip_stamp.so
+Run:   MCMCHIP_LIB=mcmc.jl_amd/mcmchip/libmcmc_hip_stamp.so python3 scripts/glm_stamps.py [d] [n] [chains]
 Prints, per phase of a 16-observation tile, the median shader cycles over workgroups 0..3, waves and tiles 8..23
 of the last evaluation: eta (loop top -> partial stored), b1 (barrier 1), elem (-> weights stored), b2, g (G
 MFMAs issued), dma (vmcnt(0) on the next tile), b3, and the whole tile."""

@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
-"""Phase timing of glm_mala1ws's tile loop (dev tool; a GLM_WS_STAMP build of glm_mala1.hip, glm.hip WS_STAMP).
+"""Phase timing of glm_mala1ws's tile loop (dev tool; a GLM_WS_STAMP build of glm_mala1ws.hip: glm_stamps.hpp WS_STAMP).
 
-Build:  hipcc ... -mllvm -amdgpu-mfma-vgpr-form -DGLM_WS_STAMP -c csrc/kernels/glm_mala1.hip -o build_ab/glm_mala1_stamp.o
-        and link it with the other objects into mcmchip/ab/libmcmc_hip_wsstamp.so
+Build:  hipcc ... -mllvm -amdgpu-mfma-vgpr-form -DGLM_WS_STAMP -c csrc/kernels/glm_mala1ws.hip -o build_ab/glm_mala1ws_stamp.o
+        (that unit's Makefile flags plus -DGLM_WS_STAMP) and link it with the other objects into mcmchip/ab/libmcmc_hip_wsstamp.so
 Run:    MCMCHIP_LIB=mcmc.jl_amd/mcmchip/ab/libmcmc_hip_wsstamp.so python3 scripts/ws_stamps.py
 Config 3's workload (logistic n = 1000, d = 128, MALA(0.001), 262 144 chains), two steps; prints, for the M waves
 (MFMA) and the V waves (elementwise), the median shader cycles of each phase of a 16-observation tile over
 workgroups 0..3, their waves and tiles 8..23 of the last launch:
   M: eta (eta_{t+1} MFMAs + its LDS store), g (G_{t-1} MFMAs issued), bar (barrier wait), tile
-  V: stage (tile t+2 to LDS, t+3 loads issued), terms (eta_t read, the logistic terms), rstore, bar, tile"""
+  V: stage (tile t+2's LDS-DMA issued), terms (eta_t read, the logistic terms), rstore, bar, tile"""
 import ctypes as ct
 import json
 import os
