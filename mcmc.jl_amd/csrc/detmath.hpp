@@ -6,7 +6,7 @@
 //   * the whole library is compiled with -ffp-contract=off; each fused
 //     multiply-add is an explicit __builtin_fma;
 //   * '/' and sqrt are the IEEE correctly-rounded operations (hipcc's default
-//     f64 lowering; checked on the device by tests/test_gpu_detmath.py);
+//     f64 lowering; checked on the device by tests/test_gpu_parity.py test_device_detmath_bitwise);
 //   * no OCML transcendentals (their last-ulp behaviour differs from glibc).
 //
 // The reference draws with Julia's global dSFMT + ziggurat (src/samplers/RWM.jl:59,

@@ -1,5 +1,5 @@
 // util.hip -- small device helpers: fills, layout transposes and the
-// deterministic-math probes used by the parity tests (tests/test_gpu_detmath.py).
+// deterministic-math probes used by the parity tests (tests/test_gpu_parity.py test_device_detmath_bitwise).
 #include "../common.hpp"
 #include "../detmath.hpp"
 
