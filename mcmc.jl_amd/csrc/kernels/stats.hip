@@ -258,6 +258,8 @@ __global__ __launch_bounds__(256, 2) void k_ess_reg(EssArgs a) {
     // correctly rounded 1/n and q0 faithful, q0 + (s - n q0) rn rounds to the correctly rounded s / n (Markstein's
     // theorem; no underflow here): the IEEE quotient orc_ess computes, for 3 operations instead of the ~11 of a
     // division (tests/test_oracle.py checks the identity on half a billion quotients, near-exact ones included).
+    // Bitwise parity with orc_ess is claimed for normal-range sums: where z^2 is subnormal (|x| below about 2^-500)
+    // the residual fma underflows and the result can differ from the IEEE quotient at a tie.
     const double rn = 1.0 / nd;
     auto qdiv = [&](double x) {
         const double q0 = x * rn;
