@@ -94,7 +94,8 @@ enum {
 };
 
 /* samplers */
-enum { MCMC_RWM = 1, MCMC_MALA = 2, MCMC_HMC = 3, MCMC_HMCDA = 4, MCMC_RAM = 5, MCMC_NUTS = 6, MCMC_SMMALA = 7 };
+enum { MCMC_RWM = 1, MCMC_MALA = 2, MCMC_HMC = 3, MCMC_HMCDA = 4, MCMC_RAM = 5, MCMC_NUTS = 6, MCMC_SMMALA = 7,
+       MCMC_PMALA = 8 };
 
 typedef struct mcmc_ctx mcmc_ctx;
 typedef struct mcmc_model mcmc_model;
@@ -108,7 +109,12 @@ typedef struct {
                                 v = exp(-eta^2 - logcdf(eta) - logcdf(-eta) - log 2 pi); LOGISTIC the expected Fisher
                                 information plus the prior precision, v = p (1 - p) for either link_sign (the metric of
                                 Girolami & Calderhead 2011 for this model; the reference's logistic example passes no
-                                tensor).  Any other kind answers MCMC_E_UNSUPPORTED                     */
+                                tensor);
+                                3: gradient, tensor and the tensor's derivatives (hasdtensor(model), mcmcmodels.jl:21):
+                                slab i of dG is X' diag(w o X[:, i]) X, w = dv / d eta: PROBIT the example's
+                                deriv_tensor as written (probit_regression.jl:52-68), LOGISTIC p (1 - p) (1 - 2p) for
+                                link_sign = +1 and its negative for -1.  A model with 3 serves everything a model
+                                with 2 does.  With 2 or 3 any other kind answers MCMC_E_UNSUPPORTED        */
     int64_t d;               /* parameter vector size (model.size)                               */
     const double* init;      /* [d]  model.init                                                  */
     const double* scale;     /* [d]  model.scale (NULL -> ones)                                   */
@@ -124,13 +130,15 @@ typedef struct {
 } mcmc_model_desc;
 
 typedef struct {
-    int32_t kind;            /* MCMC_RWM | MCMC_MALA | MCMC_HMC | MCMC_HMCDA | MCMC_RAM | MCMC_NUTS | MCMC_SMMALA */
+    int32_t kind;            /* MCMC_RWM | MCMC_MALA | MCMC_HMC | MCMC_HMCDA | MCMC_RAM | MCMC_NUTS | MCMC_SMMALA |
+                                MCMC_PMALA                                                        */
     double scale;            /* RWM, RAM: scale (RWM.jl:25, RAM.jl:23)                             */
-    double drift_step;       /* MALA: driftStep (MALA.jl:51); SMMALA: driftStep (SMMALA.jl:24)     */
+    double drift_step;       /* MALA: driftStep (MALA.jl:51); SMMALA: driftStep (SMMALA.jl:24);
+                                PMALA: driftStep (PMALA.jl:26)                                    */
     int64_t n_leaps;         /* HMC: nLeaps (HMC.jl:54); NUTS: maxdoublings (NUTS.jl:31)          */
     double leap_step;        /* HMC: leapStep (HMC.jl:55)                                          */
     double rate, len, shrinkage, t0, step;   /* HMCDA (HMCDA.jl:25-29); rate: RAM target rate (RAM.jl:24) */
-    int32_t tuner;           /* 0: nothing; 1: EmpiricalMCMCTuner (MALA, HMC, SMMALA)              */
+    int32_t tuner;           /* 0: nothing; 1: EmpiricalMCMCTuner (MALA, HMC, SMMALA, PMALA)       */
     int64_t adapt_step, max_step;            /* EmpMCTuner (samplers.jl:33-37)                      */
     double target_path, target_rate;
     int64_t max_leaps;       /* HMCDA/HMC-tuner safety cap on leapfrogs per step (0 -> 1<<20)      */
@@ -181,8 +189,15 @@ int mcmc_model_eval(mcmc_model* model, int64_t nchains, const double* x, double*
 /* model.evalallt (likmodel.jl): log-target, gradient and the metric tensor G of x[d][nchains]; host pointers, lp and
  * grad may be NULL.  G is symmetric and packed like the RAM factor: element (r, c), c <= r, of chain k at
  * G[(r(r+1)/2 + c) * nchains + k] (d(d+1)/2 * nchains doubles).  lp and grad are mcmc_model_eval's bit for bit.  A model
- * created without has_gradient == 2 answers MCMC_E_NEEDS_GRADIENT, "model has no tensor function"; built for d <= 16. */
+ * created with has_gradient < 2 answers MCMC_E_NEEDS_GRADIENT, "model has no tensor function"; built for d <= 16. */
 int mcmc_model_eval_tensor(mcmc_model* model, int64_t nchains, const double* x, double* lp, double* grad, double* G);
+/* model.evalalldt (likmodel.jl:27): evalallt's outputs (lp, grad and G may be NULL; mcmc_model_eval_tensor's bit for
+ * bit) and the derivatives of G: d slabs, each packed like G, element (r, c), c <= r, of slab i of chain k at
+ * dG[((i * d(d+1)/2) + r(r+1)/2 + c) * nchains + k] (d * d(d+1)/2 * nchains doubles).  A model created with
+ * has_gradient < 3 answers MCMC_E_NEEDS_GRADIENT, "model has no function of tensor derivatives"; d > 16
+ * MCMC_E_UNSUPPORTED.  An inspection path: the PMALA step loop never forms the slabs. */
+int mcmc_model_eval_dtensor(mcmc_model* model, int64_t nchains, const double* x, double* lp, double* grad, double* G,
+                            double* dG);
 
 /* ---- sampler config validation (the reference constructors' @asserts) ---- */
 int mcmc_sampler_validate(const mcmc_sampler_cfg* cfg);
@@ -206,7 +221,13 @@ int mcmc_runner_validate(const mcmc_runner_cfg* cfg);
  * not finite MCMC_E_INIT_OUT_OF_SUPPORT.  Outputs, tuner (EmpiricalMALATune) and tuner_state are MALA's; evals count one
  * per step plus the initial one.  A proposal out of support, or whose G or h invG fails a pivot, is rejected (the
  * reference would throw out of chol).  mcmc_chains_set_state keeps invG and firstTerm of the previous position (the
- * :reset hook as written, SMMALA.jl:54-57); mcmc_run_seqmc refuses SMMALA targets. */
+ * :reset hook as written, SMMALA.jl:54-57); mcmc_run_seqmc refuses SMMALA targets.
+ * PMALA (PMALA.jl:42-141): SMMALA's models, sizes, outputs, tuner and departures, on a model with tensor derivatives
+ * (has_gradient == 3; otherwise MCMC_E_NEEDS_GRADIENT, "PMALA sampler requires model with function of tensor
+ * derivatives", after the gradient and tensor checks).  The drift is (h/2)(firstTerm - c), c = sum_i invG dG_i invG[:, i],
+ * formed without the slabs as invG X' (w o q), q_o = x_o' invG x_o.  c is state beside SMMALA's: recomputed by
+ * mcmc_chains_reset, copied by mcmc_chains_fork, left as it is by mcmc_chains_set_state (the :reset hook as written,
+ * PMALA.jl:63-66); mcmc_run_seqmc refuses PMALA targets. */
 int mcmc_chains_create(mcmc_model* model, const mcmc_sampler_cfg* sampler, int64_t nchains,
                        int64_t chain_offset, uint64_t seed, const double* init_x, mcmc_chains** out);
 int mcmc_chains_destroy(mcmc_chains* chains);
@@ -225,7 +246,7 @@ int mcmc_chains_fork(mcmc_chains* src, int64_t first, int64_t count, mcmc_chains
 /* steps consumed so far (the sampler's own loop counter i). */
 int mcmc_chains_steps_done(mcmc_chains* chains, int64_t* steps);
 /* per-chain adaptive state after the last run, [nchains] each (any may be NULL): step = the current step size
- * (MALA / SMMALA driftStep under EmpiricalMALATune, HMC leapStep under EmpiricalHMCTune, HMCDA leapStep, HMCDA.jl:136,140);
+ * (MALA / SMMALA / PMALA driftStep under EmpiricalMALATune, HMC leapStep under EmpiricalHMCTune, HMCDA leapStep, HMCDA.jl:136,140);
  * step_bar = HMCDA's dual-averaged dualLeapStep (HMCDA.jl:138); nleaps = the tuned HMC nLeaps (HMC.jl:42).
  * NUTS: step = epsilon, step_bar = exp(log epsilon_bar) (NUTS.jl:169-172).
  * A quantity the sampler does not adapt reads NaN (steps) or 0 (nleaps). */
@@ -239,6 +260,11 @@ int mcmc_chains_evals(mcmc_chains* chains, int64_t* evals);
  * element (r, c), c <= r, of chain k at S[(r(r+1)/2 + c) * nchains + k]; host buffer of
  * d(d+1)/2 * nchains doubles.  MCMC_E_INVALID_ARG for other samplers. */
 int mcmc_chains_ram_factor(mcmc_chains* chains, double* S);
+/* SMMALA / PMALA: the sampler's state beside the position and its log-target, host buffers, any may be NULL: grad,
+ * first_term and corr (PMALA's c; MCMC_E_INVALID_ARG for SMMALA) [d][nchains]; G and invG packed like
+ * mcmc_model_eval_tensor's G.  MCMC_E_INVALID_ARG for other samplers. */
+int mcmc_chains_manifold_state(mcmc_chains* chains, double* grad, double* G, double* invG, double* first_term,
+                               double* corr);
 /* steps fused per kernel launch (0 = whole run in one launch, the default). */
 int mcmc_chains_set_steps_per_launch(mcmc_chains* chains, int64_t steps_per_launch);
 /* The burnin the samplers' adaptation sees, apart from the kept range of mcmc_run_serialmc.  The reference's

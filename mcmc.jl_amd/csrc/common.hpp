@@ -13,7 +13,8 @@ enum DistKind : int32_t {
     DK_NORMAL = 1, DK_UNIFORM = 2, DK_WEIBULL = 3, DK_BETA = 4, DK_TDIST = 5, DK_EXPONENTIAL = 6, DK_GAMMA = 7,
     DK_CAUCHY = 8, DK_LOGNORMAL = 9, DK_LAPLACE = 10
 };
-enum SamplerKind : int32_t { SK_RWM = 1, SK_MALA = 2, SK_HMC = 3, SK_HMCDA = 4, SK_RAM = 5, SK_NUTS = 6, SK_SMMALA = 7 };
+enum SamplerKind : int32_t { SK_RWM = 1, SK_MALA = 2, SK_HMC = 3, SK_HMCDA = 4, SK_RAM = 5, SK_NUTS = 6, SK_SMMALA = 7,
+                            SK_PMALA = 8 };
 
 // Model parameters as the kernels see them (device pointers).
 struct ModelArgs {
@@ -72,6 +73,8 @@ struct ChainState {
     double* sm_ft;
     double* sm_pG;              // SMMALA: the proposal's tensor and inverse (dead between steps)
     double* sm_pinvG;
+    double* pm_c;               // PMALA: the drift correction c = sum_i invG dG_i invG[:, i] at x [d][ld]; PMALA keeps
+                                //   SMMALA's five arrays too
 };
 
 // One launch of the fused step kernel.

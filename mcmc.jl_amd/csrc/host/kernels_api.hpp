@@ -53,6 +53,13 @@ hipError_t mcmc_launch_smmala_eval(const mcmc::KernelArgs& a, const double* xin,
                                    double* invG, double* ft, int check, hipStream_t st);
 hipError_t mcmc_launch_smmala_step(const mcmc::KernelArgs& a, hipStream_t st);
 int mcmc_smmala_max_d();
+// PMALA on the same models and sizes (pmala.hip).  dtensor: evalalldt, lp / g / G (any may be NULL) as
+// mcmc_launch_smmala_eval's and dG [d][d(d+1)/2][ld].  corr: the drift correction st.pm_c of the state's position from
+// st.sm_invG (after mcmc_launch_smmala_eval has formed it)
+hipError_t mcmc_launch_pmala_dtensor(const mcmc::KernelArgs& a, const double* xin, double* lp, double* g, double* G,
+                                     double* dG, hipStream_t st);
+hipError_t mcmc_launch_pmala_corr(const mcmc::KernelArgs& a, hipStream_t st);
+hipError_t mcmc_launch_pmala_step(const mcmc::KernelArgs& a, hipStream_t st);
 // RAM on regression targets, 32 < d <= 1024 (glm_ram_wave.hip): per step the eval kernel and the accept / factor-update
 // kernel; u [C][ustride], nz [C], xprop [d][ld], lpp [C] are the device buffers between them.  st2 (may be null):
 // a second stream on which half of a large batch runs, forked from and joined back to st by the two events

@@ -252,6 +252,9 @@ extern "C" int mcmc_sampler_validate(const mcmc_sampler_cfg* s) {
         case MCMC_SMMALA:
             if (!(s->drift_step > 0)) return fail(MCMC_E_INVALID_ARG, "SMMALA drift step should be > 0"); // SMMALA.jl:27
             break;
+        case MCMC_PMALA:
+            if (!(s->drift_step > 0)) return fail(MCMC_E_INVALID_ARG, "PMALA drift step should be > 0"); // PMALA.jl:30
+            break;
         case MCMC_HMC:
             if (!(s->n_leaps > 0)) return fail(MCMC_E_INVALID_ARG, "inner steps should be > 0");        // HMC.jl:60
             if (!(s->leap_step > 0)) return fail(MCMC_E_INVALID_ARG, "inner steps scaling should be > 0"); // HMC.jl:61
@@ -360,7 +363,9 @@ extern "C" int mcmc_model_create(mcmc_ctx* ctx, const mcmc_model_desc* desc, mcm
     m->has_gradient = desc->has_gradient;
     // has_gradient == 2: gradient and metric tensor (hastensor(m), mcmcmodels.jl:20); built for the probit model
     // (examples/probit_regression.jl:44-49) and the logistic model (expected Fisher information + prior precision)
-    if (desc->has_gradient == 2 && desc->kind != MCMC_MODEL_PROBIT && desc->kind != MCMC_MODEL_LOGISTIC) {
+    // has_gradient == 3: the tensor's derivatives too (hasdtensor(m), mcmcmodels.jl:21): the probit example's
+    // deriv_tensor (examples/probit_regression.jl:52-68) and d[p (1 - p)] / d eta for the logistic model
+    if (desc->has_gradient >= 2 && desc->kind != MCMC_MODEL_PROBIT && desc->kind != MCMC_MODEL_LOGISTIC) {
         delete m;
         return fail(MCMC_E_UNSUPPORTED, "this model kind has no tensor function (built: PROBIT, LOGISTIC)");
     }
@@ -648,7 +653,7 @@ extern "C" int mcmc_model_eval_tensor(mcmc_model* m, int64_t nchains, const doub
                                       double* G) {
     if (!m || !x || !G) return fail(MCMC_E_INVALID_ARG, "NULL argument");
     if (nchains <= 0) return fail(MCMC_E_INVALID_ARG, "nchains should be > 0");
-    if (m->has_gradient != 2) return fail(MCMC_E_NEEDS_GRADIENT, "model has no tensor function");
+    if (m->has_gradient < 2) return fail(MCMC_E_NEEDS_GRADIENT, "model has no tensor function");
     mcmc_ctx* ctx = m->ctx;
     if (int r = set_device(ctx)) return r;
     const int d = m->args.d;
@@ -688,13 +693,67 @@ extern "C" int mcmc_model_eval_tensor(mcmc_model* m, int64_t nchains, const doub
     return rc;
 }
 
+// model.evalalldt (likmodel.jl:27): evalallt's outputs (lp, grad and G may be NULL) and the tensor's derivatives, d
+// slabs packed like G: element (r, c), c <= r, of slab i of chain k at dG[((i nr + r(r+1)/2 + c) * nchains + k],
+// nr = d(d+1)/2
+extern "C" int mcmc_model_eval_dtensor(mcmc_model* m, int64_t nchains, const double* x, double* lp, double* grad,
+                                       double* G, double* dG) {
+    if (!m || !x || !dG) return fail(MCMC_E_INVALID_ARG, "NULL argument");
+    if (nchains <= 0) return fail(MCMC_E_INVALID_ARG, "nchains should be > 0");
+    if (m->has_gradient < 3) return fail(MCMC_E_NEEDS_GRADIENT, "model has no function of tensor derivatives");
+    mcmc_ctx* ctx = m->ctx;
+    if (int r = set_device(ctx)) return r;
+    const int d = m->args.d;
+    if (d > mcmc_smmala_max_d())
+        return fail(MCMC_E_UNSUPPORTED, "the tensor derivatives are built for d <= " + std::to_string(mcmc_smmala_max_d()));
+    const int64_t ld = round_up(nchains, 64);
+    const size_t nr = (size_t)d * (size_t)(d + 1) / 2;
+    double *dcols = nullptr, *dx = nullptr, *dlp = nullptr, *dg = nullptr, *dGG = nullptr, *ddG = nullptr;
+    hipStream_t st = ctx->stream;
+    int rc = MCMC_OK;
+    do {
+        if ((rc = dmalloc(&dcols, (size_t)d * nchains))) break;
+        if ((rc = dmalloc(&dx, (size_t)d * ld))) break;
+        if ((rc = dmalloc(&dlp, (size_t)ld))) break;
+        if ((rc = dmalloc(&dg, (size_t)d * ld))) break;
+        if ((rc = dmalloc(&dGG, nr * (size_t)ld))) break;
+        if ((rc = dmalloc(&ddG, (size_t)d * nr * (size_t)ld))) break;
+        hipError_t e = hipMemcpyAsync(dcols, x, (size_t)d * nchains * 8, hipMemcpyHostToDevice, st);
+        if (e == hipSuccess) e = mcmc_copy_cols(dx, ld, dcols, nchains, d, nchains, st);
+        KernelArgs a = base_args(m, nchains, ld);
+        if (e == hipSuccess) e = mcmc_launch_pmala_dtensor(a, dx, dlp, dg, dGG, ddG, st);
+        if (e == hipSuccess && lp) e = hipMemcpyAsync(lp, dlp, (size_t)nchains * 8, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && grad)
+            e = hipMemcpy2DAsync(grad, (size_t)nchains * 8, dg, (size_t)ld * 8, (size_t)nchains * 8, (size_t)d,
+                                 hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && G)
+            e = hipMemcpy2DAsync(G, (size_t)nchains * 8, dGG, (size_t)ld * 8, (size_t)nchains * 8, nr,
+                                 hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipMemcpy2DAsync(dG, (size_t)nchains * 8, ddG, (size_t)ld * 8, (size_t)nchains * 8, (size_t)d * nr,
+                                 hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = fail(MCMC_E_HIP, std::string("model eval dtensor: ") + hipGetErrorString(e));
+    } while (0);
+    (void)hipStreamSynchronize(st);
+    dfree(dcols);
+    dfree(dx);
+    dfree(dlp);
+    dfree(dg);
+    dfree(dGG);
+    dfree(ddG);
+    return rc;
+}
+
 // ------------------------------------------------------------------ chains
+static bool is_manifold(int32_t kind) { return kind == SK_SMMALA || kind == SK_PMALA; }
+
 static void free_state(mcmc_chains* c) {
     ChainState& s = c->st;
     dfree(s.x); dfree(s.lp); dfree(s.g); dfree(s.t_step); dfree(s.t_bar); dfree(s.t_h);
     dfree(s.t_leaps); dfree(s.t_acc); dfree(s.t_prop); dfree(s.ram_L); dfree(s.mom);
     dfree(s.t_mu); dfree(s.nuts_wv); dfree(s.nuts_ws);
-    dfree(s.sm_G); dfree(s.sm_invG); dfree(s.sm_ft); dfree(s.sm_pG); dfree(s.sm_pinvG);
+    dfree(s.sm_G); dfree(s.sm_invG); dfree(s.sm_ft); dfree(s.sm_pG); dfree(s.sm_pinvG); dfree(s.pm_c);
     s = ChainState{};
 }
 
@@ -707,6 +766,7 @@ static hipError_t launch_chain_step(const mcmc_chains* c, const KernelArgs& a, h
     }
     if (c->sa.kind == SK_NUTS) return mcmc_launch_nuts(a, 0, st);
     if (c->sa.kind == SK_SMMALA) return mcmc_launch_smmala_step(a, st);
+    if (c->sa.kind == SK_PMALA) return mcmc_launch_pmala_step(a, st);
     return launch_step(c->layout, a, st);
 }
 
@@ -727,7 +787,7 @@ static void stream_args(const mcmc_chains* c, KernelArgs& a) {
 // one device-scope atomic per wave on a single address serialises at the memory side (32 768 of them per 2^20-chain
 // launch of the pair kernel, ~10 ns apart) and held a short launch's tail for hundreds of microseconds.
 static bool evals_on_host(const mcmc_chains* c) {
-    return c->sa.kind == SK_RWM || c->sa.kind == SK_MALA || c->sa.kind == SK_RAM || c->sa.kind == SK_SMMALA;
+    return c->sa.kind == SK_RWM || c->sa.kind == SK_MALA || c->sa.kind == SK_RAM || is_manifold(c->sa.kind);
 }
 
 // Regression HMC / HMCDA: the chains' order for the next run, longest trajectory first.  A 16-chain MFMA tile runs
@@ -794,14 +854,19 @@ static int init_state(mcmc_chains* c) {
         HIP_TRY(mcmc_broadcast_cols(c->st.x, c->ld, m->d_init, d, c->C, st));
     }
     KernelArgs a = base_args(m, c->C, c->ld);
-    if (sa.kind == SK_SMMALA) {
+    if (is_manifold(sa.kind)) {
         // evalallt at the start, invG and firstTerm = invG grad (SMMALA.jl:62-67); a failed pivot sets the error word
         HIP_TRY(mcmc_launch_smmala_eval(a, c->st.x, c->st.lp, c->st.g, c->st.sm_G, c->st.sm_invG, c->st.sm_ft, 1, st));
+        if (sa.kind == SK_PMALA) {                 // sum(secondTerm, 2) of the start (PMALA.jl:77-80)
+            KernelArgs ac = a;
+            ac.st = c->st;
+            HIP_TRY(mcmc_launch_pmala_corr(ac, st));
+        }
         c->h_evals = c->C;
     } else {
         HIP_TRY(launch_eval(c->layout, a, c->st.x, c->st.lp, c->st.g, 1, st));
     }
-    if ((sa.kind == SK_MALA || sa.kind == SK_SMMALA) && sa.tuner) HIP_TRY(mcmc_fill_f64(c->st.t_step, c->C, sa.drift_step, st));
+    if ((sa.kind == SK_MALA || is_manifold(sa.kind)) && sa.tuner) HIP_TRY(mcmc_fill_f64(c->st.t_step, c->C, sa.drift_step, st));
     if (sa.kind == SK_HMC && sa.tuner) {
         HIP_TRY(mcmc_fill_f64(c->st.t_step, c->C, sa.leap_step, st));
         HIP_TRY(mcmc_fill_i32(c->st.t_leaps, c->C, (int32_t)sa.n_leaps, st));
@@ -861,11 +926,15 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
                                         " (the d x d jump factor of every chain is kept in HBM)");
     if (s->kind != MCMC_RWM && s->kind != MCMC_RAM && !m->has_gradient) {
         const char* nm = s->kind == MCMC_MALA ? "MALA" : s->kind == MCMC_HMC ? "HMC" : s->kind == MCMC_NUTS ? "NUTS"
-                         : s->kind == MCMC_SMMALA ? "SMMALA" : "HMCDA";
+                         : s->kind == MCMC_SMMALA ? "SMMALA" : s->kind == MCMC_PMALA ? "PMALA" : "HMCDA";
         return fail(MCMC_E_NEEDS_GRADIENT, std::string(nm) + " sampler requires model with gradient function");
     }
-    if (s->kind == MCMC_SMMALA && m->has_gradient != 2)                                                  // SMMALA.jl:51
+    if (s->kind == MCMC_SMMALA && m->has_gradient < 2)                                                   // SMMALA.jl:51
         return fail(MCMC_E_NEEDS_GRADIENT, "SMMALA sampler requires model with tensor function");
+    if (s->kind == MCMC_PMALA && m->has_gradient < 2)                                                    // PMALA.jl:54
+        return fail(MCMC_E_NEEDS_GRADIENT, "PMALA sampler requires model with tensor function");
+    if (s->kind == MCMC_PMALA && m->has_gradient < 3)                                                    // PMALA.jl:55
+        return fail(MCMC_E_NEEDS_GRADIENT, "PMALA sampler requires model with function of tensor derivatives");
     mcmc_ctx* ctx = m->ctx;
     if (int r = set_device(ctx)) return r;
     const int d = m->args.d;
@@ -875,6 +944,10 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
         return fail(MCMC_E_UNSUPPORTED, "SMMALA is built for d <= " + std::to_string(mcmc_smmala_max_d()) +
                                             " (the metric tensor of a 16-chain tile is held in registers); d = " +
                                             std::to_string(d));
+    if (s->kind == MCMC_PMALA && d > mcmc_smmala_max_d())
+        return fail(MCMC_E_UNSUPPORTED, "PMALA is built for d <= " + std::to_string(mcmc_smmala_max_d()) +
+                                            " (SMMALA's geometry: the metric tensor of a 16-chain tile is held in "
+                                            "registers); d = " + std::to_string(d));
     if (s->kind == MCMC_NUTS) {
         if (model_is_glm(m))
             return fail(MCMC_E_UNSUPPORTED, "NUTS is not built for the regression models (built: the separable and joint "
@@ -922,14 +995,16 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
     if (c->layout == LAYOUT_GLM && d > 128 && (sa.kind == SK_HMC || sa.kind == SK_HMCDA))   // d-sliced: momentum
         if (int r = dmalloc(&c->st.mom, (size_t)mcmc_glm_d_pad(d) * c->ld)) return bail(r);      // parking (glm_hmc)
     if (int r = dmalloc(&c->st.lp, nc)) return bail(r);
-    const bool tuned = sa.tuner && (sa.kind == SK_MALA || sa.kind == SK_HMC || sa.kind == SK_SMMALA);
-    if (sa.kind == SK_SMMALA) {
+    const bool tuned = sa.tuner && (sa.kind == SK_MALA || sa.kind == SK_HMC || is_manifold(sa.kind));
+    if (is_manifold(sa.kind)) {
         const size_t nr = (size_t)d * (size_t)(d + 1) / 2 * (size_t)c->ld;
         if (int r = dmalloc(&c->st.sm_G, nr)) return bail(r);
         if (int r = dmalloc(&c->st.sm_invG, nr)) return bail(r);
         if (int r = dmalloc(&c->st.sm_pG, nr)) return bail(r);
         if (int r = dmalloc(&c->st.sm_pinvG, nr)) return bail(r);
         if (int r = dmalloc(&c->st.sm_ft, nst)) return bail(r);
+        if (sa.kind == SK_PMALA)
+            if (int r = dmalloc(&c->st.pm_c, nst)) return bail(r);
     }
     if (tuned || sa.kind == SK_HMCDA || sa.kind == SK_NUTS)
         if (int r = dmalloc(&c->st.t_step, nc)) return bail(r);
@@ -1049,8 +1124,9 @@ extern "C" int mcmc_chains_set_state(mcmc_chains* c, const double* x, double* lp
     hipError_t e = hipMemcpyAsync(dcols, x, (size_t)d * C * 8, hipMemcpyHostToDevice, st);
     if (e == hipSuccess) e = cols_to_state(c->layout, c->st.x, c->ld, dcols, C, d, C, st);
     KernelArgs a = base_args(m, C, c->ld);
-    // SMMALA's :reset hook (SMMALA.jl:54-57) re-evaluates evalallt only: invG and firstTerm stay as they were
-    if (e == hipSuccess && c->sa.kind == SK_SMMALA)
+    // SMMALA's :reset hook (SMMALA.jl:54-57) re-evaluates evalallt only: invG and firstTerm stay as they were; PMALA's
+    // (PMALA.jl:63-66) likewise, secondTerm (the correction c) too
+    if (e == hipSuccess && is_manifold(c->sa.kind))
         e = mcmc_launch_smmala_eval(a, c->st.x, c->st.lp, c->st.g, c->st.sm_G, nullptr, nullptr, 0, st);
     else if (e == hipSuccess) e = launch_eval(c->layout, a, c->st.x, c->st.lp, c->st.g, 0, st);
     if (e == hipSuccess && lp) e = hipMemcpyAsync(lp, c->st.lp, (size_t)C * 8, hipMemcpyDeviceToHost, st);
@@ -1111,6 +1187,7 @@ extern "C" int mcmc_chains_fork(mcmc_chains* src, int64_t first, int64_t count, 
     hipError_t e = cols(c->st.x, src->st.x);
     if (e == hipSuccess) e = cols(c->st.g, src->st.g);
     if (e == hipSuccess) e = cols(c->st.sm_ft, src->st.sm_ft);
+    if (e == hipSuccess) e = cols(c->st.pm_c, src->st.pm_c);
     auto packed = [&](double* dst, const double* from) -> hipError_t {      // SMMALA: [d(d+1)/2][ld]
         if (!dst || !from) return hipSuccess;
         return hipMemcpy2DAsync(dst, (size_t)c->ld * 8, from + first, (size_t)src->ld * 8, (size_t)count * 8,
@@ -1179,6 +1256,30 @@ extern "C" int mcmc_chains_evals(mcmc_chains* c, int64_t* evals) {
     unsigned long long v = 0;
     HIP_TRY(d2h(ctx, &v, c->d_evals, sizeof v));
     *evals = (int64_t)v + c->h_evals;
+    return MCMC_OK;
+}
+
+// SMMALA / PMALA: the state beside pars and logTarget, host buffers (any may be NULL): grad, ft, c [d][C]; G, invG
+// packed [d(d+1)/2][C]
+extern "C" int mcmc_chains_manifold_state(mcmc_chains* c, double* grad, double* G, double* invG, double* ft,
+                                          double* corr) {
+    if (!c) return fail(MCMC_E_INVALID_ARG, "chains is NULL");
+    if (!is_manifold(c->sa.kind)) return fail(MCMC_E_INVALID_ARG, "chains do not run the SMMALA or PMALA sampler");
+    if (corr && c->sa.kind != SK_PMALA) return fail(MCMC_E_INVALID_ARG, "SMMALA keeps no drift correction");
+    mcmc_ctx* ctx = c->model->ctx;
+    if (int r = set_device(ctx)) return r;
+    const size_t d = (size_t)c->model->args.d, nr = d * (d + 1) / 2, C = (size_t)c->C;
+    auto rows = [&](double* dst, const double* src, size_t n) -> hipError_t {
+        if (!dst) return hipSuccess;
+        return hipMemcpy2DAsync(dst, C * 8, src, (size_t)c->ld * 8, C * 8, n, hipMemcpyDeviceToHost, ctx->stream);
+    };
+    hipError_t e = rows(grad, c->st.g, d);
+    if (e == hipSuccess) e = rows(G, c->st.sm_G, nr);
+    if (e == hipSuccess) e = rows(invG, c->st.sm_invG, nr);
+    if (e == hipSuccess) e = rows(ft, c->st.sm_ft, d);
+    if (e == hipSuccess) e = rows(corr, c->st.pm_c, d);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) return fail(MCMC_E_HIP, std::string("manifold state: ") + hipGetErrorString(e));
     return MCMC_OK;
 }
 
@@ -1643,6 +1744,9 @@ extern "C" int mcmc_run_seqmc(mcmc_chains* const* targets, int32_t ntargets, int
             return fail(MCMC_E_INVALID_ARG, "Models do not have the same parameter vector size");  // SeqMC.jl:49
         if (targets[t]->model->ctx != ctx) return fail(MCMC_E_INVALID_ARG, "targets live on different contexts");
         if (targets[t]->C != npart) return fail(MCMC_E_INVALID_ARG, "every target needs nchains == npart");
+        if (targets[t]->sa.kind == SK_PMALA)
+            return fail(MCMC_E_UNSUPPORTED, "SeqMC does not run PMALA targets: the sampler's reset hook keeps invG, "
+                                            "firstTerm and secondTerm of the chain's previous position (PMALA.jl:63-66)");
         if (targets[t]->sa.kind == SK_SMMALA)
             return fail(MCMC_E_UNSUPPORTED, "SeqMC does not run SMMALA targets: the sampler's reset hook keeps invG and "
                                             "firstTerm of the chain's previous position (SMMALA.jl:54-57)");

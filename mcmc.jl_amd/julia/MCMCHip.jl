@@ -27,6 +27,7 @@ const MODEL_ISO_NORMAL_DOT, MODEL_NORMAL_DSL, MODEL_LOGISTIC, MODEL_LINEAR = 1, 
 const MODEL_ABS_NORMAL_DSL, MODEL_DIST_DSL, MODEL_PROBIT, MODEL_DIST_OBS, MODEL_OU = 5, 6, 7, 8, 9
 const RWM_K, MALA_K, HMC_K, HMCDA_K, RAM_K = 1, 2, 3, 4, 5
 const SMMALA_K = 7            # MCMC_SMMALA: needs a model with has_gradient = 2 (gradient and metric tensor)
+const PMALA_K = 8             # MCMC_PMALA: needs a model with has_gradient = 3 (gradient, tensor and tensor derivatives)
 
 check(st) = st == 0 ? nothing :
     error(unsafe_string(ccall((:mcmc_last_error, lib), Cstring, ())))   # reference @assert text

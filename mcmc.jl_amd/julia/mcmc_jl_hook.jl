@@ -87,6 +87,7 @@ type MCMCHipModel <: MCMCModel
   scale::Vector{Float64}          # model.scale
   pmap::Dict                      # model.pmap: column names of the chain's DataFrames (SerialMC.jl:70-80)
   gradient::Bool
+  tensor::Bool; dtensor::Bool     # hastensor / hasdtensor (mcmcmodels.jl:20-21): :probit and :logistic, d <= 16
   mu::Float64; sigma::Float64     # :normal, :absnormal; :dist parameters p1, p2
   dist::Symbol
   prior_sigma::Float64; noise_sigma::Float64; link_sign::Float64
@@ -107,11 +108,13 @@ end
 #                                                               examples/ornstein.jl:19-30 (the series x in Y; the
 #                                                               chain's columns tau, sigma, mu as model(ex, tau=...) names)
 function hipmodel(kind::Symbol; init::Vector{Float64}=Float64[], scale::Vector{Float64}=Float64[],
-                  name::Symbol=:vars, gradient::Bool=true, mu::Float64=0., sigma::Float64=1., dist::Symbol=:Normal,
+                  name::Symbol=:vars, gradient::Bool=true, tensor::Bool=false, dtensor::Bool=false, mu::Float64=0., sigma::Float64=1., dist::Symbol=:Normal,
                   prior_sigma::Float64=1., noise_sigma::Float64=1., link_sign::Float64=1.,
                   X::Matrix{Float64}=zeros(0, 0), Y::Vector{Float64}=Float64[], device::Int=0,
                   pmap::Union(Dict, Nothing)=nothing)
   @assert haskey(HIP_MODEL_KINDS, kind) "unknown GPU model kind $kind"
+  @assert !tensor || gradient "a model with a tensor function needs its gradient function"
+  @assert !dtensor || tensor "a model with a function of tensor derivatives needs its tensor function"
   if kind == :logistic || kind == :linear || kind == :probit
     @assert size(X, 1) == length(Y) "X has $(size(X, 1)) rows, Y $(length(Y)) entries"
     isempty(init) && (init = zeros(size(X, 2)))
@@ -129,12 +132,17 @@ function hipmodel(kind::Symbol; init::Vector{Float64}=Float64[], scale::Vector{F
   if pmap == nothing
     pmap = d == 1 ? {name => (1, ())} : {name => (1, (d,))}     # one scalar or vector variable, as model() builds
   end
-  MCMCHipModel(kind, d, copy(init), copy(scale), pmap, gradient, mu, sigma, dist, prior_sigma, noise_sigma,
+  MCMCHipModel(kind, d, copy(init), copy(scale), pmap, gradient, tensor, dtensor, mu, sigma, dist, prior_sigma, noise_sigma,
                link_sign, X, Y, device)
 end
 
+# has_gradient of the descriptor: 0 eval only, 1 gradient, 2 gradient and tensor (SMMALA), 3 tensor derivatives too (PMALA)
+hip_has_gradient(m::MCMCHipModel) = m.dtensor ? 3 : m.tensor ? 2 : m.gradient ? 1 : 0
+hastensor(m::MCMCHipModel) = m.tensor
+hasdtensor(m::MCMCHipModel) = m.dtensor
+
 function hip_desc(m::MCMCHipModel, Xr::Vector{Float64})
-  HipModelDesc(HIP_MODEL_KINDS[m.kind], m.gradient ? 1 : 0, m.size, pointer(m.init), pointer(m.scale),
+  HipModelDesc(HIP_MODEL_KINDS[m.kind], hip_has_gradient(m), m.size, pointer(m.init), pointer(m.scale),
                m.mu, m.sigma, m.prior_sigma, m.noise_sigma, m.link_sign, length(m.Y),
                isempty(Xr) ? convert(Ptr{Float64}, C_NULL) : pointer(Xr),
                isempty(m.Y) ? convert(Ptr{Float64}, C_NULL) : pointer(m.Y),
@@ -152,6 +160,9 @@ hip_sampler(s::MALA) = hip_cfg(2, 0., s.driftStep, 0, 0., 0., 0., 0., 0., 0., hi
 # SMMALA (MCMC_SMMALA = 7): MALA's fields; the library needs a model created with has_gradient = 2 (a tensor function),
 # built for the probit and logistic catalogue models with d <= 16
 hip_sampler(s::SMMALA) = hip_cfg(7, 0., s.driftStep, 0, 0., 0., 0., 0., 0., 0., hip_tuner(s.tuner), 0)
+# PMALA (MCMC_PMALA = 8): MALA's fields; the library needs a model created with has_gradient = 3 (tensor derivatives:
+# hipmodel(...; tensor=true, dtensor=true)), built for the probit and logistic catalogue models with d <= 16
+hip_sampler(s::PMALA) = hip_cfg(8, 0., s.driftStep, 0, 0., 0., 0., 0., 0., 0., hip_tuner(s.tuner), 0)
 hip_sampler(s::HMC) = hip_cfg(3, 0., 0., s.nLeaps, s.leapStep, 0., 0., 0., 0., 0., hip_tuner(s.tuner), 0)
 hip_sampler(s::HMCDA) = hip_cfg(4, 0., 0., 0, 0., s.rate, s.len, s.shrinkage, s.t0, s.step, hip_tuner(nothing), 0)
 hip_sampler(s::RAM) = hip_cfg(5, s.scale, 0., 0, 0., s.rate, 0., 0., 0., 0., hip_tuner(nothing), 0)
@@ -366,7 +377,7 @@ function hip_run_group(m::MCMCHipModel, s::MCMCSampler, r::SerialMC, n::Int, see
   end
 end
 
-has_grads(s::MCMCSampler) = isa(s, MALA) || isa(s, SMMALA) || isa(s, HMC) || isa(s, HMCDA) || isa(s, NUTS)
+has_grads(s::MCMCSampler) = isa(s, MALA) || isa(s, SMMALA) || isa(s, PMALA) || isa(s, HMC) || isa(s, HMCDA) || isa(s, NUTS)
 # the sampler's own diagnostics of kept step j, chain c: {"accept"} for the Metropolis samplers, NUTS's
 # {"epsilon", "ndoublings"} (NUTS.jl:177, which has no "accept")
 function hip_step_diag(s::MCMCSampler, o::HipRun, j::Int, c::Int)

@@ -42,6 +42,7 @@ SAMPLER_HMCDA = 4
 SAMPLER_RAM = 5
 SAMPLER_NUTS = 6
 SAMPLER_SMMALA = 7
+SAMPLER_PMALA = 8
 
 VAR_IMSE = 1
 VAR_IPSE = 2
@@ -54,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "mcmc_last_error", "mcmc_abi_version", "mcmc_device_count",
     "mcmc_ctx_create", "mcmc_ctx_destroy", "mcmc_ctx_synchronize",
     "mcmc_model_create", "mcmc_model_destroy", "mcmc_model_eval", "mcmc_model_eval_tensor",
+    "mcmc_model_eval_dtensor", "mcmc_chains_manifold_state",
     "mcmc_sampler_validate", "mcmc_runner_validate",
     "mcmc_chains_create", "mcmc_chains_destroy", "mcmc_chains_reset", "mcmc_chains_set_state", "mcmc_chains_fork",
     "mcmc_chains_steps_done", "mcmc_chains_evals",
@@ -152,6 +154,8 @@ def load() -> ct.CDLL:
         "mcmc_model_destroy": (ct.c_int, [P]),
         "mcmc_model_eval": (ct.c_int, [P, i64, dp, dp, dp]),
         "mcmc_model_eval_tensor": (ct.c_int, [P, i64, dp, dp, dp, dp]),
+        "mcmc_model_eval_dtensor": (ct.c_int, [P, i64, dp, dp, dp, dp, dp]),
+        "mcmc_chains_manifold_state": (ct.c_int, [P, dp, dp, dp, dp, dp]),
         "mcmc_sampler_validate": (ct.c_int, [ct.POINTER(SamplerCfg)]),
         "mcmc_runner_validate": (ct.c_int, [ct.POINTER(RunnerCfg)]),
         "mcmc_chains_create": (ct.c_int, [P, ct.POINTER(SamplerCfg), i64, i64, u64, dp, pp]),

@@ -33,7 +33,7 @@ from ._lib import check, dptr
 __all__ = [
     "IsoNormalDot", "NormalDSL", "AbsNormalDSL", "DistDSL", "DistObsDSL", "LogisticRegression", "LinearRegression", "ProbitRegression", "vaso_data",
     "OrnsteinUhlenbeck", "ou_series", "MCMCLikelihoodModel", "model",
-    "RWM", "MALA", "SMMALA", "HMC", "HMCDA", "RAM", "NUTS", "EmpMCTuner", "EmpiricalMCMCTuner", "SerialMC", "MCMCTask", "MCMCChain",
+    "RWM", "MALA", "SMMALA", "PMALA", "HMC", "HMCDA", "RAM", "NUTS", "EmpMCTuner", "EmpiricalMCMCTuner", "SerialMC", "MCMCTask", "MCMCChain",
     "run", "resume", "device_count",
 ]
 
@@ -194,7 +194,7 @@ class MCMCLikelihoodModel:
     """MCMCLikelihoodModel (likmodel.jl:20-57): target + init + scale + pmap, uploaded once per GPU."""
 
     def __init__(self, target, init, scale=1.0, gradient: bool = False, pmap: Optional[dict] = None,
-                 tensor: bool = False):
+                 tensor: bool = False, dtensor: bool = False):
         self.target = target
         init = [float(init)] if np.isscalar(init) else init                   # likmodel.jl:112
         self.init = _f64(init).reshape(-1)
@@ -210,6 +210,9 @@ class MCMCLikelihoodModel:
         self.has_tensor = bool(tensor)             # hastensor(m) = m.evalt != nothing (mcmcmodels.jl:20)
         if self.has_tensor and not self.has_gradient:
             raise AssertionError("a model with a tensor function needs its gradient function (gradient=True)")
+        self.has_dtensor = bool(dtensor)           # hasdtensor(m) = m.evaldt != nothing (mcmcmodels.jl:21)
+        if self.has_dtensor and not self.has_tensor:
+            raise AssertionError("a model with a function of tensor derivatives needs its tensor function (tensor=True)")
         self.pmap = pmap if pmap is not None else {"pars": (1, (self.size,))}  # likmodel.jl:118
         if hasattr(target, "X"):
             if target.X.ndim != 2 or target.X.shape[1] != self.size:
@@ -233,7 +236,7 @@ class MCMCLikelihoodModel:
         t = self.target
         desc = _lib.ModelDesc()
         desc.kind = t.kind
-        desc.has_gradient = 2 if self.has_tensor else 1 if self.has_gradient else 0
+        desc.has_gradient = 3 if self.has_dtensor else 2 if self.has_tensor else 1 if self.has_gradient else 0
         desc.d = self.size
         desc.init = dptr(self.init)
         desc.scale = dptr(self.scale)
@@ -286,6 +289,28 @@ class MCMCLikelihoodModel:
             return lp[0], g[:, 0], G[:, :, 0]
         return lp, g, G
 
+    def evalalldt(self, x, device: int = 0):
+        """model.evalalldt on a batch (likmodel.jl:27): x [d] or [d, nchains] -> (lp, grad, G, dG), dG [d, d, d] or
+        [d, d, d, nchains] with dG[:, :, i] the derivative of G along coordinate i (probit:
+        examples/probit_regression.jl:52-68; logistic: X' diag(p (1 - p) (1 - 2p) X[:, i]) X, negated for link_sign -1)."""
+        xa = np.asarray(x, dtype=np.float64)
+        single = xa.ndim == 1
+        xa = np.ascontiguousarray(xa.reshape(self.size, -1))
+        C, d = xa.shape[1], self.size
+        nr = d * (d + 1) // 2
+        lp, g, Gp, dGp = np.empty(C), np.empty((d, C)), np.empty((nr, C)), np.empty((d, nr, C))
+        check(_lib.load().mcmc_model_eval_dtensor(self._handle(device), C, dptr(xa), dptr(lp), dptr(g), dptr(Gp),
+                                                  dptr(dGp)))
+        G = np.empty((d, d, C))
+        dG = np.empty((d, d, d, C))
+        for r in range(d):
+            for c in range(r + 1):
+                G[r, c] = G[c, r] = Gp[r * (r + 1) // 2 + c]
+                dG[r, c] = dG[c, r] = dGp[:, r * (r + 1) // 2 + c]
+        if single:
+            return lp[0], g[:, 0], G[:, :, 0], dG[:, :, :, 0]
+        return lp, g, G, dG
+
     def __mul__(self, sampler):
         return _ModelSampler(self, sampler)
 
@@ -299,7 +324,7 @@ class MCMCLikelihoodModel:
 
 
 def model(f, mtype: str = "likelihood", init=None, scale=1.0, gradient: bool = False,
-          grad=None, tensor: bool = False, **dsl_init) -> MCMCLikelihoodModel:
+          grad=None, tensor: bool = False, dtensor: bool = False, **dsl_init) -> MCMCLikelihoodModel:
     """model() entry point (mcmcmodels.jl:27-33).
 
     Function style (likmodel.jl:100-143): model(IsoNormalDot(), init=ones(3)) has no gradient, like
@@ -318,8 +343,8 @@ def model(f, mtype: str = "likelihood", init=None, scale=1.0, gradient: bool = F
     if grad is not None and grad is not False:
         gradient = True
     # tensor=True: the model's metric tensor (model(...; tensor=...), examples/probit_regression.jl:69); built for
-    # ProbitRegression and LogisticRegression
-    return MCMCLikelihoodModel(f, init, scale=scale, gradient=gradient, tensor=bool(tensor))
+    # ProbitRegression and LogisticRegression; dtensor=True: its derivatives too (model(...; dtensor=...), the same line)
+    return MCMCLikelihoodModel(f, init, scale=scale, gradient=gradient, tensor=bool(tensor), dtensor=bool(dtensor))
 
 
 # ------------------------------------------------------------------ samplers
@@ -409,6 +434,23 @@ class SMMALA(MALA):
             driftStep = scale
         if not driftStep > 0:
             raise AssertionError("SMMALA drift step should be > 0")            # SMMALA.jl:27
+        self.driftStep, self.tuner = float(driftStep), tuner
+
+
+class PMALA(MALA):
+    """Position-dependent MALA (PMALA.jl:25-37): MALA's constructor forms (PMALA(s::MALATuner) names an undefined `t`,
+    PMALA.jl:36; the intended PMALA(1.0, tuner) is built); needs a model with tensor derivatives."""
+    kind = _lib.SAMPLER_PMALA
+    uses_tensor = True
+    uses_dtensor = True
+
+    def __init__(self, driftStep: Union[float, EmpiricalMCMCTuner] = 1.0, tuner=None, scale: Optional[float] = None):
+        if isinstance(driftStep, EmpiricalMCMCTuner):
+            driftStep, tuner = 1.0, driftStep
+        if scale is not None:
+            driftStep = scale
+        if not driftStep > 0:
+            raise AssertionError("PMALA drift step should be > 0")             # PMALA.jl:30
         self.driftStep, self.tuner = float(driftStep), tuner
 
 
@@ -658,6 +700,8 @@ class MCMCTask:
             raise AssertionError(f"{name} sampler requires model with gradient function")
         if getattr(sampler, "uses_tensor", False) and not getattr(model, "has_tensor", False):           # SMMALA.jl:51
             raise AssertionError(f"{type(sampler).__name__} sampler requires model with tensor function")
+        if getattr(sampler, "uses_dtensor", False) and not getattr(model, "has_dtensor", False):         # PMALA.jl:55
+            raise AssertionError(f"{type(sampler).__name__} sampler requires model with function of tensor derivatives")
         self.model, self.sampler, self.runner = model, sampler, runner
         self.nchains, self.device = int(nchains), int(device)
         self.seed = None if seed is None else int(seed)
@@ -805,6 +849,27 @@ class MCMCTask:
                 check(_lib.load().mcmc_chains_ram_factor(c, part.ctypes.data))
                 packed[:, f:f + n] = part
         return unpack_ram_factor(packed, d)
+
+    def manifold_state(self) -> dict:
+        """SMMALA / PMALA: the sampler's state beside the position (mcmc_chains_manifold_state): "grad" and
+        "first_term" [d, nchains], "G" and "invG" packed lower rows [d(d+1)/2, nchains], and for PMALA "corr", the
+        drift correction c [d, nchains]."""
+        if self._h is None:
+            raise AssertionError("the task has not run")
+        d, C = self.model.size, self.nchains
+        nr = d * (d + 1) // 2
+        names = ["grad", "G", "invG", "first_term"] + (["corr"] if getattr(self.sampler, "uses_dtensor", False) else [])
+        rows = {"grad": d, "G": nr, "invG": nr, "first_term": d, "corr": d}
+        out = {k: np.empty((rows[k], C)) for k in names}
+        for c, f, n in self.blocks():
+            if c is None:
+                continue
+            part = {k: np.empty((rows[k], n)) for k in names}
+            check(_lib.load().mcmc_chains_manifold_state(c, *[dptr(part.get(k)) for k in
+                                                              ("grad", "G", "invG", "first_term", "corr")]))
+            for k in names:
+                out[k][:, f:f + n] = part[k]
+        return out
 
     def reset(self) -> None:
         if self._h is not None:
