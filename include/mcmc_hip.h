@@ -388,6 +388,30 @@ enum { MCMC_VAR_IMSE = 1, MCMC_VAR_IPSE = 2, MCMC_VAR_BM = 3 };
 int mcmc_stats_ess(mcmc_ctx* ctx, const double* samples, int64_t nkept, int64_t d, int64_t nchains, int32_t vtype,
                    int64_t maxlag, int64_t batchlen, int32_t on_device, double* ess, double* var);
 
+/* describe(chain) (src/stats/summary.jl:24-55) of samples [nkept][d][nchains], in one read of the samples, plus the
+ * pooled row a many-chain run is read by.  Both tables are optional; at least one must be asked for.
+ *   per_chain [6][d][nchains] or NULL: min, mean, max, mcerror, ess, actime of every (parameter j, chain c) series,
+ *     summary.jl:35-42 as written: mean = sum / n, variid = (ss / (n - 1)) / n, varimse the MCMC_VAR_IMSE variance
+ *     (maxlag <= 0 -> nkept - 1), mcerror = sqrt(varimse), ess = (n variid) / varimse (bit for bit mcmc_stats_ess's),
+ *     actime = varimse / variid; min and max with -0 returned as +0, a NaN sample passed over.
+ *   pooled [MCMC_DESCRIBE_NPOOLED + nprobs][d] or NULL: rows min, mean, max, mcerror, ess, rhat (MCMC_DESCRIBE_*), then
+ *     the nprobs exact quantiles (Julia's quantile, type 7) of the nkept * nchains values of each parameter.  mean: the
+ *     mean over chains of the chain means; mcerror = sqrt(sum_c varimse_c) / C' and ess = sum_c ess_c over the C' chains
+ *     whose varimse and ess are finite and varimse > 0; rhat (Gelman-Rubin) = sqrt(((n - 1)/n W + B/n) / W) with
+ *     W = mean_c ss_c / (n - 1), B/n = var_c(mean_c) (divisor C - 1), NaN when nchains = 1 or W = 0.  Sums over chains
+ *     run in one order fixed by nchains alone.
+ *   nbad [d] or NULL (filled with the pooled table): the chains left out of mcerror and ess (a chain that never moved,
+ *     or whose first Geyer pair is <= 0); they still count in mean, min, max, rhat and the quantiles.
+ * probs: nprobs <= MCMC_DESCRIBE_MAXPROBS probabilities in [0, 1].  nkept < 2, nprobs out of range, a probability
+ * outside [0, 1] or both tables NULL answer MCMC_E_INVALID_ARG.  on_device != 0: every pointer is device memory on
+ * ctx's GPU. */
+enum { MCMC_DESCRIBE_MIN = 0, MCMC_DESCRIBE_MEAN = 1, MCMC_DESCRIBE_MAX = 2, MCMC_DESCRIBE_MCERROR = 3,
+       MCMC_DESCRIBE_ESS = 4, MCMC_DESCRIBE_RHAT = 5, MCMC_DESCRIBE_ACTIME = 5 /* per_chain's last column */,
+       MCMC_DESCRIBE_NPOOLED = 6, MCMC_DESCRIBE_MAXPROBS = 8 };
+int mcmc_stats_describe(mcmc_ctx* ctx, const double* samples, int64_t nkept, int64_t d, int64_t nchains, int64_t maxlag,
+                        int32_t on_device, double* per_chain, const double* probs, int32_t nprobs, double* pooled,
+                        int64_t* nbad);
+
 /* Zero-variance control-variate estimators (src/stats/zv.jl:8-68) of every chain of samples / grads
  * [nkept][d][nchains].  With z = -grads/2 and w_t the k control variates of kept step t -- MCMC_ZV_LINEAR: k = d,
  * w = z; MCMC_ZV_QUADRATIC: k = d(d+3)/2, the z_j, then 2 z_j x_j - 1, then x_i z_j + x_j z_i for i < j in zv.jl's

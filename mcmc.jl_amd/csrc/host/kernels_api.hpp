@@ -78,6 +78,13 @@ hipError_t mcmc_seqmc_store(int64_t N, int d, const double* pars, const double* 
 // effective sample size of every (parameter, chain) series of samples [n][d][C] (stats.hip)
 hipError_t mcmc_launch_ess(const double* samples, int64_t n, int64_t d, int64_t C, int32_t vtype, int64_t maxlag,
                            int64_t batchlen, double* ess, double* var, hipStream_t st);
+// describe's tables (describe.hip) of samples [n][d][C], every pointer but probs device memory: per_chain [6][d][C]
+// or NULL; pooled [6 + nprobs][d] or NULL (then probs, nprobs and nbad are not looked at); nbad [d] or NULL; ws a
+// workspace of mcmc_describe_ws_bytes.  IMSE with maxlag as mcmc_launch_ess takes it
+size_t mcmc_describe_ws_bytes(int64_t d, int64_t C, int has_per_chain, int has_pooled, int32_t nprobs);
+hipError_t mcmc_launch_describe(const double* samples, int64_t n, int64_t d, int64_t C, int64_t maxlag,
+                                double* per_chain, const double* probs, int32_t nprobs, double* pooled, int64_t* nbad,
+                                void* ws, hipStream_t st);
 // zero-variance estimators (zv.hip): order 1 linear, 2 quadratic; samples x and gradients g [n][d][C] -> zv [n][d][C],
 // coef [k][d][C] (or NULL), info [C] (or NULL).  d <= mcmc_zv_max_d(order); k = mcmc_zv_k(order, d)
 hipError_t mcmc_launch_zv(int order, const double* x, const double* g, int64_t n, int d, int64_t C, double* zv,

@@ -1870,6 +1870,77 @@ extern "C" int mcmc_stats_ess(mcmc_ctx* ctx, const double* samples, int64_t nkep
     return rc;
 }
 
+extern "C" int mcmc_stats_describe(mcmc_ctx* ctx, const double* samples, int64_t nkept, int64_t d, int64_t nchains,
+                                   int64_t maxlag, int32_t on_device, double* per_chain, const double* probs,
+                                   int32_t nprobs, double* pooled, int64_t* nbad) {
+    // the shape checks come first and need no device (tests/test_describe_cpu.py runs them without one)
+    if (!per_chain && !pooled) return fail(MCMC_E_INVALID_ARG, "describe: ask for per_chain, pooled or both");
+    if (nkept < 2 || d <= 0 || nchains <= 0) return fail(MCMC_E_INVALID_ARG, "need nkept >= 2, d > 0, nchains > 0");
+    if (d > 65535) return fail(MCMC_E_UNSUPPORTED, "d > 65535");
+    if (maxlag <= 0) maxlag = nkept - 1;
+    if (maxlag > nkept - 1) return fail(MCMC_E_INVALID_ARG, "maxlag should be < nkept");
+    if (!pooled) nprobs = 0;
+    if (nprobs < 0 || nprobs > MCMC_DESCRIBE_MAXPROBS)
+        return fail(MCMC_E_INVALID_ARG, "describe: nprobs = " + std::to_string(nprobs) + " is not in 0.." +
+                                            std::to_string(MCMC_DESCRIBE_MAXPROBS));
+    if (nprobs > 0 && !probs) return fail(MCMC_E_INVALID_ARG, "describe: nprobs > 0 and probs is NULL");
+    double hp[MCMC_DESCRIBE_MAXPROBS] = {0};
+    auto probs_ok = [&]() {
+        for (int i = 0; i < nprobs; ++i)
+            if (!(hp[i] >= 0.0 && hp[i] <= 1.0))
+                return fail(MCMC_E_INVALID_ARG, "describe: probability " + std::to_string(hp[i]) + " is not in [0, 1]");
+        return (int)MCMC_OK;
+    };
+    if (!on_device) {
+        for (int i = 0; i < nprobs; ++i) hp[i] = probs[i];
+        if (int r = probs_ok()) return r;
+    }
+    if (!ctx || !samples) return fail(MCMC_E_INVALID_ARG, "NULL argument");
+    if (int r = set_device(ctx)) return r;
+    hipStream_t st = ctx->stream;
+    if (on_device && nprobs > 0) {
+        if (d2h(ctx, hp, probs, (size_t)nprobs * 8) != hipSuccess) return fail(MCMC_E_HIP, "probs download failed");
+        if (int r = probs_ok()) return r;
+    }
+    const size_t dC = (size_t)d * (size_t)nchains, ns = (size_t)nkept * dC;
+    const size_t npool = (size_t)(MCMC_DESCRIBE_NPOOLED + nprobs) * (size_t)d;
+    const double* ds = samples;
+    double *dsb = nullptr, *dpc = per_chain, *dpo = pooled;
+    int64_t* dnb = nbad;
+    char* ws = nullptr;
+    int rc = MCMC_OK;
+    do {
+        if (!on_device) {
+            dpc = dpo = nullptr;
+            dnb = nullptr;
+            if ((rc = dmalloc(&dsb, ns))) break;
+            if (per_chain && (rc = dmalloc(&dpc, 6 * dC))) break;
+            if (pooled && (rc = dmalloc(&dpo, npool))) break;
+            if (pooled && nbad && (rc = dmalloc(&dnb, (size_t)d))) break;
+            if (h2d(ctx, dsb, samples, ns * 8) != hipSuccess) { rc = fail(MCMC_E_HIP, "samples upload failed"); break; }
+            ds = dsb;
+        }
+        if ((rc = dmalloc(&ws, mcmc_describe_ws_bytes(d, nchains, per_chain != nullptr, pooled != nullptr, nprobs))))
+            break;
+        hipError_t e = mcmc_launch_describe(ds, nkept, d, nchains, maxlag, dpc, hp, nprobs, dpo, pooled ? dnb : nullptr,
+                                            ws, st);
+        if (e == hipSuccess && !on_device && per_chain) e = d2h(ctx, per_chain, dpc, 6 * dC * 8);
+        if (e == hipSuccess && !on_device && pooled) e = d2h(ctx, pooled, dpo, npool * 8);
+        if (e == hipSuccess && !on_device && pooled && nbad) e = d2h(ctx, nbad, dnb, (size_t)d * 8);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) rc = fail(MCMC_E_HIP, std::string("describe: ") + hipGetErrorString(e));
+    } while (0);
+    (void)hipStreamSynchronize(st);
+    dfree(ws);
+    if (!on_device) {
+        dfree(dsb);
+        dfree(dpc);
+        dfree(dpo);
+        dfree(dnb);
+    }
+    return rc;
+}
+
 extern "C" int mcmc_stats_zv(mcmc_ctx* ctx, int32_t order, const double* samples, const double* grads, int64_t nkept,
                              int64_t d, int64_t nchains, int32_t on_device, double* zv, double* coef, int32_t* info) {
     if (!ctx || !samples || !grads || !zv) return fail(MCMC_E_INVALID_ARG, "NULL argument");

@@ -127,6 +127,19 @@ function stats_zv(ctx, smp::Array{Float64,3}, grd::Array{Float64,3}; order = 1)
     zv, coef, info
 end
 
+# describe (summary.jl:24-55) of every chain, and the pooled rows: samples of size (C, d, nkept) -> the per-chain table
+# (C, d, 6): min, mean, max, mcerror, ess, actime; the pooled table (d, 6 + length(probs)): min, mean, max, mcerror, ess,
+# rhat, then the exact pooled quantiles; nbad (d): the chains left out of the pooled mcerror and ess
+function stats_describe(ctx, smp::Array{Float64,3}; probs = [0.025, 0.5, 0.975], maxlag = 0)
+    C, d, nk = size(smp)
+    p = convert(Vector{Float64}, probs)
+    per = Array{Float64}(undef, C, d, 6); pooled = Array{Float64}(undef, d, 6 + length(p)); nbad = zeros(Int64, d)
+    check(ccall((:mcmc_stats_describe, lib), Cint, (Ptr{Cvoid}, Ptr{Float64}, Int64, Int64, Int64, Int64, Int32,
+        Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Int64}), ctx, smp, nk, d, C, maxlag, 0, per, p, length(p),
+        pooled, nbad))
+    per, pooled, nbad
+end
+
 # ---- prun (runners.jl:35-42, examples/parallel_serialmc.jl) -> one chain batch over a node's GPUs
 # mcmc_group_*: contiguous 64-chain-aligned blocks, one per listed device, driven from this one Julia thread
 # (a library worker thread per block); results bit-identical to one context running every chain.  Blocks are whole

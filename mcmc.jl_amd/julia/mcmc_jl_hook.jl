@@ -29,6 +29,8 @@
 #                                                  the ESS of every chain of a GPU batch in one mcmc_stats_ess call.
 #   linearZv(cs::Array{MCMCChain}), quadraticZv(cs::Array{MCMCChain})   zv.jl:8-68 -- new methods likewise: the ZV
 #                                                  estimators of every chain of a GPU batch in one mcmc_stats_zv call.
+#   describe(cs::Array{MCMCChain})   summary.jl:24-55 -- a new method likewise: every chain's table and the pooled rows
+#                                                  (mean, MC error, ESS, Rhat, quantiles) in one mcmc_stats_describe call.
 # Runner semantics.  A GPU task produces every step (run_serialmc applies the kept range itself), in chunks of at
 # most the task runner's len; the samplers' adaptation reads the task's own runner (MALA.jl:116, HMC.jl:167,
 # HMCDA.jl:133-141), so the task runner's burnin is set as the chains' tuner burnin (mcmc_chains_set_tuner_burnin)
@@ -43,7 +45,7 @@
 
 const hiplib = haskey(ENV, "MCMCHIP_LIB") ? ENV["MCMCHIP_LIB"] : "libmcmc_hip"
 
-export MCMCHipModel, hipmodel, hip_run_batch, hip_run_arrays, hip_srand, hip_ess, hip_zv
+export MCMCHipModel, hipmodel, hip_run_batch, hip_run_arrays, hip_srand, hip_ess, hip_zv, hip_describe
 
 # ---- C structs (include/mcmc_hip.h), isbits, C layout
 immutable HipModelDesc            # mcmc_model_desc
@@ -690,6 +692,59 @@ function ess(cs::Array{MCMCChain}; vtype::Symbol=:imse, maxlag::Int=0, batchlen:
   x = Float64[cs[c].samples[k, j] for c in 1:length(cs), j in 1:d, k in 1:nk]
   e, _ = hip_ess(x; vtype=vtype, maxlag=maxlag, batchlen=batchlen, device=cs[1].task.model.device)
   [vec(e[c, :]) for c in 1:length(cs)]
+end
+
+# ---- describe on the device (summary.jl:24-55; mcmc_stats_describe)
+const HIP_DESCRIBE_STATS = ["Min", "Mean", "Max", "MC Error", "ESS", "AC Time"]
+
+# samples as hip_run_arrays returns them, (C, d, nkept): the per-chain table (C, d, 6) in HIP_DESCRIBE_STATS' order, the
+# pooled table (d, 6 + length(probs)): min, mean, max, mcerror, ess, rhat, then the exact pooled quantiles, and nbad (d):
+# the chains left out of the pooled mcerror and ess
+function hip_describe(x::Array{Float64, 3}; probs::Vector{Float64}=[0.025, 0.5, 0.975], maxlag::Int=0, device::Int=0)
+  C, d, nk = size(x)
+  per, pooled, nbad = Array(Float64, C, d, 6), Array(Float64, d, 6 + length(probs)), Array(Int64, d)
+  hipcheck(ccall((:mcmc_stats_describe, hiplib), Cint,
+                 (Ptr{Void}, Ptr{Float64}, Int64, Int64, Int64, Int64, Int32, Ptr{Float64}, Ptr{Float64}, Int32,
+                  Ptr{Float64}, Ptr{Int64}),
+                 hip_context(device).h, x, nk, d, C, maxlag, 0, per, probs, length(probs), pooled, nbad))
+  per, pooled, nbad
+end
+
+# describe(c) of every chain of an array, printed as summary.jl:44-53 prints one chain, then the pooled rows; chains of
+# GPU tasks with equal shapes go to the device in one call, anything else chain by chain
+describe(cs::Array{MCMCChain}) = describe(STDOUT, cs)
+function describe(io, cs::Array{MCMCChain}; probs::Vector{Float64}=[0.025, 0.5, 0.975])
+  gpu = !isempty(cs) && all(c -> isa(c.task, MCMCTask) && isa(c.task.model, MCMCHipModel), cs)
+  if gpu
+    nk, d = size(cs[1].samples)
+    gpu = all(c -> size(c.samples) == (nk, d), cs)
+  end
+  if !gpu
+    for c in cs
+      describe(io, c)
+    end
+    return
+  end
+  x = Float64[cs[c].samples[k, j] for c in 1:length(cs), j in 1:d, k in 1:nk]
+  per, pooled, nbad = hip_describe(x; probs=probs, device=cs[1].task.model.device)
+  names = colnames(cs[1].samples)
+  for c in 1:length(cs), j in 1:d
+    println(io, names[j], " (chain ", c, ")")
+    for i = 1:6
+      println(io, string(rpad(HIP_DESCRIBE_STATS[i], 10, " "), " ", string(per[c, j, i])))
+    end
+    println(io, "NAs        0")                      # summary.jl:49-51: a GPU batch's samples hold no NA
+    println(io, "NA%        0.0%")
+    println(io, )
+  end
+  pnames = vcat(["Min", "Mean", "Max", "MC Error", "ESS", "Rhat"], [string("Q ", p) for p in probs])
+  for j in 1:d
+    println(io, names[j], " (pooled over ", length(cs), " chains, ", nbad[j], " left out of MC Error and ESS)")
+    for i = 1:length(pnames)
+      println(io, string(rpad(pnames[i], 10, " "), " ", string(pooled[j, i])))
+    end
+    println(io, )
+  end
 end
 
 # ---- ZV estimators on the device (zv.jl:8-68; mcmc_stats_zv)

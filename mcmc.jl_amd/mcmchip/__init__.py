@@ -15,6 +15,7 @@ from .seqmc import SeqMC, SeqMCChain, run_seqmc, resume_seqmc  # noqa: F401
 from . import stats  # noqa: F401
 from .stats import acceptance, mean, var, ess, actime, mcvar_iid, mcvar_bm, mcvar_imse, mcvar_ipse  # noqa: F401
 from .stats import linear_zv, quadratic_zv, zv_device  # noqa: F401
+from .stats import describe, describe_device  # noqa: F401
 
 MCMCLikModel = MCMCLikelihoodModel
 __version__ = "0.1.0"

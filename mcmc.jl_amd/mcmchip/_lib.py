@@ -51,6 +51,10 @@ VAR_BM = 3
 ZV_LINEAR = 1
 ZV_QUADRATIC = 2
 
+DESCRIBE_COLUMNS = ("min", "mean", "max", "mcerror", "ess", "actime")     # per_chain [6][d][C]
+DESCRIBE_POOLED = ("min", "mean", "max", "mcerror", "ess", "rhat")        # pooled rows, then the quantiles
+DESCRIBE_MAXPROBS = 8
+
 EXPORTED_SYMBOLS = (
     "mcmc_last_error", "mcmc_abi_version", "mcmc_device_count",
     "mcmc_ctx_create", "mcmc_ctx_destroy", "mcmc_ctx_synchronize",
@@ -69,7 +73,8 @@ EXPORTED_SYMBOLS = (
     "mcmc_group_chains_set_steps_per_launch", "mcmc_group_chains_block", "mcmc_group_run_serialmc",
     "mcmc_group_last_pin_s",
     "mcmc_debug_group_inject_failure",
-    "mcmc_seqmc_validate", "mcmc_run_seqmc", "mcmc_stats_ess", "mcmc_stats_zv", "mcmc_debug_detmath", "mcmc_debug_philox",
+    "mcmc_seqmc_validate", "mcmc_run_seqmc", "mcmc_stats_ess", "mcmc_stats_describe", "mcmc_stats_zv",
+    "mcmc_debug_detmath", "mcmc_debug_philox",
     "mcmc_debug_mfma_f64", "mcmc_debug_chains_order",
 )
 
@@ -197,6 +202,8 @@ def load() -> ct.CDLL:
                                       ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.POINTER(ct.c_double)]),
         "mcmc_stats_ess": (ct.c_int, [P, ct.c_void_p, i64, i64, i64, i32, i64, i64, i32, ct.c_void_p,
                                       ct.c_void_p]),
+        "mcmc_stats_describe": (ct.c_int, [P, ct.c_void_p, i64, i64, i64, i64, i32, ct.c_void_p, ct.c_void_p, i32,
+                                           ct.c_void_p, ct.c_void_p]),
         "mcmc_stats_zv": (ct.c_int, [P, i32, ct.c_void_p, ct.c_void_p, i64, i64, i64, i32, ct.c_void_p, ct.c_void_p,
                                      ct.c_void_p]),
         "mcmc_debug_detmath": (ct.c_int, [P, ct.c_int, i64, dp, dp, dp]),

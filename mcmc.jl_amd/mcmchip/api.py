@@ -941,6 +941,19 @@ class MCMCChain:
     def nchains(self) -> int:
         return self._samples.shape[2]
 
+    def describe(self, io=None, **kw):
+        """describe(c) (summary.jl:22-55).  Samples that live on the device (a tensor [nkept, d, nchains]) go through
+        stats.describe_device and nothing crosses PCIe; with `io` the pooled rows are written to it (a table of every
+        chain is not: Describe.table() brings it to the host).  Host samples go through the numpy twin, which prints
+        the reference's table.  Either result's column(name) is [nchains, d] and table() numpy [nchains, d, 6]."""
+        from . import stats
+        if hasattr(self._samples, "data_ptr"):
+            r = stats.describe_device(self._samples, **kw)
+            if io is not None and r.pooled is not None:
+                r.write_pooled(io, getattr(self, "names", None))
+            return r
+        return stats.describe(self, io=io, **kw)
+
     def __repr__(self) -> str:                                                 # MCMC.jl:82-84
         nk, d, C = self._samples.shape
         return f"{d} parameters, {nk} samples (per parameter), {C} chain(s), {round(self.runTime, 1)} sec."

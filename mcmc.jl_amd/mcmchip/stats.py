@@ -24,7 +24,8 @@ from typing import Optional
 import numpy as np
 
 __all__ = ["acceptance", "mean", "mcvar_iid", "mcvar_bm", "mcvar_imse", "mcvar_ipse", "var", "ess", "actime",
-           "autocov", "ess_device", "ess_per_sec", "linear_zv", "quadratic_zv", "zv_device"]
+           "autocov", "ess_device", "ess_per_sec", "linear_zv", "quadratic_zv", "zv_device", "describe",
+           "describe_device", "Describe"]
 
 
 def _samples(c) -> np.ndarray:
@@ -166,6 +167,146 @@ def ess_device(c, vtype: str = "imse", maxlag: Optional[int] = None, batchlen: i
     _lib.check(lib.mcmc_stats_ess(_ctx(device), s.ctypes.data, n, d, C, _VT[vt], ml, batchlen, 0, e.ctypes.data,
                                   v.ctypes.data if v is not None else None))
     return (e.T.copy(), v.T.copy()) if return_var else e.T.copy()
+
+
+class Describe:
+    """What describe / describe_device return.
+
+    per_chain   the six columns `columns` = (min, mean, max, mcerror, ess, actime) of every series: numpy
+                [nchains, d, 6] from host samples, a device tensor [6, d, nchains] (the C-ABI layout) from a device
+                tensor, None when not asked for; column(name) [nchains, d] and table() (numpy [nchains, d, 6]) read
+                either the same way
+    pooled     {min, mean, max, mcerror, ess, rhat} -> [d]
+    quantiles   [nprobs, d], the exact pooled quantiles at `probs`
+    nbad        [d]: the chains left out of the pooled mcerror and ess"""
+    columns = ("min", "mean", "max", "mcerror", "ess", "actime")
+    rows = ("min", "mean", "max", "mcerror", "ess", "rhat")
+
+    def __init__(self, per_chain, pooled, quantiles, probs, nbad):
+        self.per_chain, self.pooled, self.quantiles, self.probs, self.nbad = per_chain, pooled, quantiles, probs, nbad
+
+    def column(self, name):
+        """one column of the per-chain table as [nchains, d] whichever path produced it: a numpy view, or a view of
+        the device tensor (nothing is copied)"""
+        i = self.columns.index(name)
+        return self.per_chain[i].T if hasattr(self.per_chain, "data_ptr") else self.per_chain[:, :, i]
+
+    def table(self) -> np.ndarray:
+        """the per-chain table as numpy [nchains, d, 6] whichever path produced it (a device table is copied to the
+        host: 48 bytes a series)"""
+        if hasattr(self.per_chain, "data_ptr"):
+            return np.ascontiguousarray(self.per_chain.cpu().numpy().transpose(2, 1, 0))
+        return self.per_chain
+
+    def write_pooled(self, io, names=None) -> None:
+        """the pooled rows and quantiles of every parameter, in the layout of the reference's per-chain table"""
+        host = lambda a: a.cpu().numpy() if hasattr(a, "data_ptr") else np.asarray(a)
+        rows = {nm: host(v) for nm, v in self.pooled.items()}
+        q, nbad = host(self.quantiles), host(self.nbad)
+        labels = dict(zip(self.rows, ("Min", "Mean", "Max", "MC Error", "ESS", "Rhat")))
+        for j in range(len(nbad)):
+            print(f"{names[j] if names else f'x{j + 1}'} (pooled, {int(nbad[j])} chain(s) left out of MC Error and ESS)",
+                  file=io)
+            for nm in self.rows:
+                print(f"{labels[nm]:<10} {float(rows[nm][j])!r}", file=io)
+            for p, row in zip(self.probs, q):
+                print(f"{'Q ' + repr(p):<10} {float(row[j])!r}", file=io)
+            print(file=io)
+
+
+def _quantile7(v_sorted: np.ndarray, p: float) -> float:
+    """Julia's quantile (type 7) on sorted values, plain multiply and add"""
+    N = len(v_sorted)
+    h = np.float64(N - 1) * np.float64(p)
+    lo = int(np.floor(h))
+    f = h - np.floor(h)
+    vlo = v_sorted[lo]
+    return vlo + f * (v_sorted[min(lo + 1, N - 1)] - vlo)
+
+
+def describe(c, io=None, probs=(0.025, 0.5, 0.975), maxlag=None) -> Describe:
+    """describe(c) (summary.jl:24-55) in numpy: per chain and parameter Min, Mean, Max, MC Error, ESS, AC Time exactly as
+    the reference forms them from mcvar_imse and var, plus the pooled rows and quantiles describe_device gives.  For
+    one chain the reference's table is printed (to `io`, default stdout); for more, only when `io` is given."""
+    import sys
+    s = _samples(c)                                            # [C, n, d]
+    C, n, d = s.shape
+    with np.errstate(all="ignore"):
+        varimse = mcvar_imse(s, maxlag)                        # summary.jl:38
+        variid = s.var(axis=1, ddof=1) / n                     # :39
+        mcerror = np.sqrt(varimse)                             # :40
+        ss = n * variid / varimse                              # :41
+        act = varimse / variid                                 # :42
+        mn, mx, mean_ = s.min(axis=1) + 0.0, s.max(axis=1) + 0.0, s.mean(axis=1)
+        per_chain = np.stack([mn, mean_, mx, mcerror, ss, act], axis=2)
+        good = np.isfinite(varimse) & np.isfinite(ss) & (varimse > 0)
+        ngood = good.sum(axis=0)
+        W = s.var(axis=1, ddof=1).mean(axis=0)
+        Bn = mean_.var(axis=0, ddof=1) if C > 1 else np.full(d, np.nan)
+        rhat = np.where((C > 1) & (W != 0), np.sqrt(((n - 1) / n * W + Bn) / np.where(W != 0, W, 1.0)), np.nan)
+        pooled = {"min": mn.min(axis=0), "mean": mean_.mean(axis=0), "max": mx.max(axis=0),
+                  "mcerror": np.sqrt(np.where(good, varimse, 0.0).sum(axis=0)) / ngood,
+                  "ess": np.where(good, ss, 0.0).sum(axis=0), "rhat": rhat}
+        flat = np.sort(s.reshape(C * n, d) + 0.0, axis=0)
+        q = np.array([[_quantile7(flat[:, j], p) for j in range(d)] for p in probs]).reshape(len(probs), d)
+    if io is None and C == 1:
+        io = sys.stdout
+    if io is not None:
+        names = getattr(c, "names", None) or [f"x{j + 1}" for j in range(d)]
+        for ch in range(C):
+            for j in range(d):
+                print(names[j] if C == 1 else f"{names[j]} (chain {ch + 1})", file=io)
+                for nm, v in zip(("Min", "Mean", "Max", "MC Error", "ESS", "AC Time"), per_chain[ch, j]):
+                    print(f"{nm:<10} {v!r}" if not isinstance(v, np.floating) else f"{nm:<10} {float(v)!r}", file=io)
+                print("NAs        0", file=io)
+                print("NA%        0.0%", file=io)
+                print(file=io)
+    return Describe(per_chain, pooled, q, tuple(probs), (C - ngood).astype(np.int64))
+
+
+def describe_device(c, probs=(0.025, 0.5, 0.975), maxlag: Optional[int] = None, device: int = 0,
+                    per_chain: bool = True, pooled: bool = True) -> Describe:
+    """describe on the GPU (kernels/describe.hip; mcmc_stats_describe): the per-chain table in one read of the samples,
+    the pooled rows from the per-chain values, exact pooled quantiles by radix select.
+
+    `c` is an MCMCChain (host samples: numpy results, the per-chain table [nchains, d, 6]) or a device tensor
+    [nkept, d, nchains] in the C-ABI layout (device tensors: the table [6, d, nchains], the pooled rows [d], the
+    quantiles [nprobs, d], nbad [d]; nothing but the few probabilities crosses PCIe)."""
+    from . import _lib
+    from .api import _ctx
+    lib = _lib.load()
+    ml = 0 if maxlag is None else int(maxlag)
+    probs = tuple(float(p) for p in probs)
+    npr, NP = len(probs), len(Describe.rows)
+    if hasattr(c, "data_ptr"):
+        import torch
+        if c.dim() != 3 or c.dtype != torch.float64 or not c.is_contiguous():
+            raise ValueError("expected a contiguous float64 tensor [nkept, d, nchains]")
+        n, d, C = c.shape
+        kw = dict(dtype=torch.float64, device=c.device)
+        pc = torch.empty((6, d, C), **kw) if per_chain else None
+        po = torch.empty((NP + npr, d), **kw) if pooled else None
+        nb = torch.empty((d,), dtype=torch.int64, device=c.device) if pooled else None
+        pr = torch.tensor(probs, **kw) if pooled and npr else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _lib.check(lib.mcmc_stats_describe(_ctx(c.device.index or 0), c.data_ptr(), n, d, C, ml, 1, ptr(pc), ptr(pr),
+                                           npr, ptr(po), ptr(nb)))
+    else:
+        s = np.ascontiguousarray(c._samples if hasattr(c, "_samples") else c, dtype=np.float64)
+        if s.ndim != 3:
+            raise ValueError("expected samples [nkept, d, nchains]")
+        n, d, C = s.shape
+        pc = np.empty((6, d, C)) if per_chain else None
+        po = np.empty((NP + npr, d)) if pooled else None
+        nb = np.empty(d, dtype=np.int64) if pooled else None
+        pr = np.array(probs, dtype=np.float64)
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        _lib.check(lib.mcmc_stats_describe(_ctx(device), s.ctypes.data, n, d, C, ml, 0, ptr(pc), ptr(pr) if npr else None,
+                                           npr, ptr(po), ptr(nb)))
+        if pc is not None:
+            pc = np.ascontiguousarray(pc.transpose(2, 1, 0))   # [nchains, d, 6], as describe's
+    rows = {nm: po[i] for i, nm in enumerate(Describe.rows)} if po is not None else None
+    return Describe(pc, rows, po[NP:] if po is not None else None, probs, nb)
 
 
 def ess_per_sec(ess_dc, seconds: float) -> float:
