@@ -259,6 +259,16 @@ extern "C" int mcmc_sampler_validate(const mcmc_sampler_cfg* s) {
             if (!(s->n_leaps > 0)) return fail(MCMC_E_INVALID_ARG, "inner steps should be > 0");        // HMC.jl:60
             if (!(s->leap_step > 0)) return fail(MCMC_E_INVALID_ARG, "inner steps scaling should be > 0"); // HMC.jl:61
             break;
+        case MCMC_RMHMC:
+            if (!(s->n_leaps > 0)) return fail(MCMC_E_INVALID_ARG, "Number of leapfrog steps should be > 0");   // RMHMC.jl:35
+            if (!(s->leap_step > 0)) return fail(MCMC_E_INVALID_ARG, "Leapfrog step size should be > 0");       // RMHMC.jl:36
+            if (!(s->t0 > 0)) return fail(MCMC_E_INVALID_ARG, "Number of Newton steps should be > 0");          // RMHMC.jl:37
+            // nNewton travels in t0, a double holding an integer
+            if (!(s->t0 <= 2147483647.0) || s->t0 != (double)(int64_t)s->t0)
+                return fail(MCMC_E_INVALID_ARG, "RMHMC: t0 carries nNewton and should hold an integer in 1 .. 2^31 - 1");
+            if (s->n_leaps > ((int64_t)1 << 20))
+                return fail(MCMC_E_UNSUPPORTED, "RMHMC is built for nLeaps <= 2^20");
+            break;
         case MCMC_RAM: {
             if (!(s->scale > 0)) return fail(MCMC_E_INVALID_ARG, "scale should be > 0");               // RAM.jl:27
             if (!(s->rate > 0.0 && s->rate < 1.0)) {
@@ -767,6 +777,7 @@ static hipError_t launch_chain_step(const mcmc_chains* c, const KernelArgs& a, h
     if (c->sa.kind == SK_NUTS) return mcmc_launch_nuts(a, 0, st);
     if (c->sa.kind == SK_SMMALA) return mcmc_launch_smmala_step(a, st);
     if (c->sa.kind == SK_PMALA) return mcmc_launch_pmala_step(a, st);
+    if (c->sa.kind == SK_RMHMC) return mcmc_launch_rmhmc_step(a, st);
     return launch_step(c->layout, a, st);
 }
 
@@ -867,7 +878,7 @@ static int init_state(mcmc_chains* c) {
         HIP_TRY(launch_eval(c->layout, a, c->st.x, c->st.lp, c->st.g, 1, st));
     }
     if ((sa.kind == SK_MALA || is_manifold(sa.kind)) && sa.tuner) HIP_TRY(mcmc_fill_f64(c->st.t_step, c->C, sa.drift_step, st));
-    if (sa.kind == SK_HMC && sa.tuner) {
+    if ((sa.kind == SK_HMC || sa.kind == SK_RMHMC) && sa.tuner) {   // EmpiricalHMCTune(nLeaps, leapStep, 0, 0)
         HIP_TRY(mcmc_fill_f64(c->st.t_step, c->C, sa.leap_step, st));
         HIP_TRY(mcmc_fill_i32(c->st.t_leaps, c->C, (int32_t)sa.n_leaps, st));
     }
@@ -926,7 +937,7 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
                                         " (the d x d jump factor of every chain is kept in HBM)");
     if (s->kind != MCMC_RWM && s->kind != MCMC_RAM && !m->has_gradient) {
         const char* nm = s->kind == MCMC_MALA ? "MALA" : s->kind == MCMC_HMC ? "HMC" : s->kind == MCMC_NUTS ? "NUTS"
-                         : s->kind == MCMC_SMMALA ? "SMMALA" : s->kind == MCMC_PMALA ? "PMALA" : "HMCDA";
+                         : s->kind == MCMC_SMMALA ? "SMMALA" : s->kind == MCMC_PMALA ? "PMALA" : s->kind == MCMC_RMHMC ? "RMHMC" : "HMCDA";
         return fail(MCMC_E_NEEDS_GRADIENT, std::string(nm) + " sampler requires model with gradient function");
     }
     if (s->kind == MCMC_SMMALA && m->has_gradient < 2)                                                   // SMMALA.jl:51
@@ -935,6 +946,10 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
         return fail(MCMC_E_NEEDS_GRADIENT, "PMALA sampler requires model with tensor function");
     if (s->kind == MCMC_PMALA && m->has_gradient < 3)                                                    // PMALA.jl:55
         return fail(MCMC_E_NEEDS_GRADIENT, "PMALA sampler requires model with function of tensor derivatives");
+    if (s->kind == MCMC_RMHMC && m->has_gradient < 2)                                                    // RMHMC.jl:65
+        return fail(MCMC_E_NEEDS_GRADIENT, "RMHMC sampler requires model with tensor function");
+    if (s->kind == MCMC_RMHMC && m->has_gradient < 3)                                                    // RMHMC.jl:66
+        return fail(MCMC_E_NEEDS_GRADIENT, "RMHMC sampler requires model with function of tensor derivatives");
     mcmc_ctx* ctx = m->ctx;
     if (int r = set_device(ctx)) return r;
     const int d = m->args.d;
@@ -946,6 +961,10 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
                                             std::to_string(d));
     if (s->kind == MCMC_PMALA && d > mcmc_smmala_max_d())
         return fail(MCMC_E_UNSUPPORTED, "PMALA is built for d <= " + std::to_string(mcmc_smmala_max_d()) +
+                                            " (SMMALA's geometry: the metric tensor of a 16-chain tile is held in "
+                                            "registers); d = " + std::to_string(d));
+    if (s->kind == MCMC_RMHMC && d > mcmc_smmala_max_d())
+        return fail(MCMC_E_UNSUPPORTED, "RMHMC is built for d <= " + std::to_string(mcmc_smmala_max_d()) +
                                             " (SMMALA's geometry: the metric tensor of a 16-chain tile is held in "
                                             "registers); d = " + std::to_string(d));
     if (s->kind == MCMC_NUTS) {
@@ -983,6 +1002,7 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
     sa.target_path = s->target_path;
     sa.target_rate = s->target_rate;
     sa.max_leaps = s->max_leaps > 0 ? s->max_leaps : (int64_t)1 << 20;
+    sa.n_newton = s->kind == MCMC_RMHMC ? (int32_t)s->t0 : 0;
     auto bail = [&](int code) {
         mcmc_chains_destroy(c);
         return code;
@@ -995,7 +1015,7 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
     if (c->layout == LAYOUT_GLM && d > 128 && (sa.kind == SK_HMC || sa.kind == SK_HMCDA))   // d-sliced: momentum
         if (int r = dmalloc(&c->st.mom, (size_t)mcmc_glm_d_pad(d) * c->ld)) return bail(r);      // parking (glm_hmc)
     if (int r = dmalloc(&c->st.lp, nc)) return bail(r);
-    const bool tuned = sa.tuner && (sa.kind == SK_MALA || sa.kind == SK_HMC || is_manifold(sa.kind));
+    const bool tuned = sa.tuner && (sa.kind == SK_MALA || sa.kind == SK_HMC || sa.kind == SK_RMHMC || is_manifold(sa.kind));
     if (is_manifold(sa.kind)) {
         const size_t nr = (size_t)d * (size_t)(d + 1) / 2 * (size_t)c->ld;
         if (int r = dmalloc(&c->st.sm_G, nr)) return bail(r);
@@ -1006,6 +1026,8 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
         if (sa.kind == SK_PMALA)
             if (int r = dmalloc(&c->st.pm_c, nst)) return bail(r);
     }
+    if (sa.kind == SK_RMHMC)                     // the trajectory's current inverse (rmhmc.hip; dead between steps)
+        if (int r = dmalloc(&c->st.sm_pinvG, (size_t)d * (size_t)(d + 1) / 2 * (size_t)c->ld)) return bail(r);
     if (tuned || sa.kind == SK_HMCDA || sa.kind == SK_NUTS)
         if (int r = dmalloc(&c->st.t_step, nc)) return bail(r);
     if (sa.kind == SK_NUTS) {
@@ -1021,7 +1043,7 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
         if (int r = dmalloc(&c->st.t_h, nc)) return bail(r);
     }
     if (tuned) {
-        if (sa.kind == SK_HMC)
+        if (sa.kind == SK_HMC || sa.kind == SK_RMHMC)
             if (int r = dmalloc(&c->st.t_leaps, nc)) return bail(r);
         if (int r = dmalloc(&c->st.t_acc, nc)) return bail(r);
         if (int r = dmalloc(&c->st.t_prop, nc)) return bail(r);
@@ -1427,6 +1449,9 @@ extern "C" int mcmc_chains_store_leaps(mcmc_chains* c, int64_t cap, double* pars
         c->leap_cap = 0;
         return MCMC_OK;
     }
+    if (c->sa.kind == SK_RMHMC)
+        return fail(MCMC_E_UNSUPPORTED, "storeLeaps is not built for RMHMC: the reference's RMHMC keeps no leapfrog "
+                                        "record (RMHMC.jl:120-155)");
     if (c->sa.kind != SK_HMC && c->sa.kind != SK_HMCDA)
         return fail(MCMC_E_INVALID_ARG, "storeLeaps needs an HMC or HMCDA sampler");
     if (cap < 0 || !grads || !mom || !lp || !H || !nleaps) return fail(MCMC_E_INVALID_ARG, "bad storeLeaps buffers");
@@ -1747,6 +1772,9 @@ extern "C" int mcmc_run_seqmc(mcmc_chains* const* targets, int32_t ntargets, int
         if (targets[t]->sa.kind == SK_PMALA)
             return fail(MCMC_E_UNSUPPORTED, "SeqMC does not run PMALA targets: the sampler's reset hook keeps invG, "
                                             "firstTerm and secondTerm of the chain's previous position (PMALA.jl:63-66)");
+        if (targets[t]->sa.kind == SK_RMHMC)
+            return fail(MCMC_E_UNSUPPORTED, "SeqMC does not run RMHMC targets: the population runner's device path is "
+                                            "built for the samplers without a metric tensor");
         if (targets[t]->sa.kind == SK_SMMALA)
             return fail(MCMC_E_UNSUPPORTED, "SeqMC does not run SMMALA targets: the sampler's reset hook keeps invG and "
                                             "firstTerm of the chain's previous position (SMMALA.jl:54-57)");

@@ -17,8 +17,9 @@
 // prior precision is constant and adds nothing.  eta is smm_tiles' chain.
 //
 // The sampler's drift correction c = sum_i invG dG_i invG[:, i] (PMALA.jl:77-80, 94) never forms the slabs:
-// sum_i dG_i invG[:, i] = X' (w o qf), qf_o = x_o' invG x_o.  pm_corr is a second pass over the staged X tiles with
-// the chain's invG in the tile's workspace W; per tile of 16 observations and per chain c of the wave's tile:
+// sum_i dG_i invG[:, i] = X' (w o qf), qf_o = x_o' invG x_o.  pm_corr is a second pass over the staged X tiles
+// (smm_device.hpp's smm_dw_tiles, which rmhmc.hip shares; the weight pm_dw and the staging live there too) with the
+// chain's invG in the tile's workspace W; per tile of 16 observations and per chain c of the wave's tile:
 //   eta           smm_tiles' MFMA chain;
 //   M = invG_c X' one v_mfma_f64_16x16x4_f64 per k-slice e: A lane (q, cl) = invG_c[cl][4q + e] (held in registers for
 //                 the whole pass, zero past d), B lane (q, cl) = X[obs cl][4q + e]; lane (q, cl) register r is
@@ -32,43 +33,6 @@
 #include "smm_device.hpp"
 
 namespace mcmc {
-
-__device__ __forceinline__ double pm_probit_dw(double eta) {
-    const double la = det_normlogcdf(eta), lb = det_normlogcdf(-eta);
-    const double e2 = eta * eta;
-    const double A = (-(e2 + kLog2Pi)) / 2.0;
-    const double v01 = det_exp((((-e2) - 2.0 * la) - lb) - kLog2Pi);
-    return v01 * (det_exp(A - lb) - 2.0 * (det_exp(A) + eta * det_exp(la)));
-}
-
-// y: the tile's response column (probit: unused; logistic: wt = s (2y - 1))
-template <bool LOGI>
-__device__ __forceinline__ double pm_dw(double eta, double y, const double (*sptab)[10]) {
-    if (LOGI) {
-        double term, rv;
-        det_logi(eta, y, term, rv, sptab);
-        const double sig = __builtin_fabs(rv);
-        const double v = sig * (1.0 - sig);
-        return (v * (1.0 - 2.0 * sig)) * (-y);
-    }
-    return pm_probit_dw(eta);
-}
-
-// first tile and the logistic term's table into LDS; every wave of the workgroup (two barriers)
-template <bool LOGI>
-__device__ __forceinline__ void pm_stage_first(const GlmArgs& a, const SmLds& S) {
-    constexpr int kHalf = kSmXS / 2;
-    const int ti = threadIdx.x < kHalf ? (int)threadIdx.x : 0;
-    __syncthreads();                                          // the previous pass's last tile has been read
-    {
-        const f64x2 v = reinterpret_cast<const f64x2*>(a.m.X)[ti];
-        if (threadIdx.x < kHalf) reinterpret_cast<f64x2*>(S.X)[ti] = v;
-    }
-    if (LOGI) {
-        for (int i = threadIdx.x; i < SP_NROWS * 10; i += 256) S.sp[i] = (&kSoftplusTab[0][0])[i];
-    }
-    __syncthreads();
-}
 
 // slab i of dG for the tile's sixteen chains into T (lane (q, cl) register r of chain c: dG_i[q + 4r][cl])
 template <bool LOGI>
@@ -123,88 +87,12 @@ __device__ __forceinline__ void pm_slab(const GlmArgs& a, const GlmPos& p, const
     }
 }
 
-// u = X' (w o qf) at the lane's coordinates x, the chains' invG in the workspace S.W (header); returns u at the lane's
-// own coordinates.  Every wave of the workgroup calls it (barriers inside).
-template <bool LOGI>
-__device__ __forceinline__ f64x4 pm_corr_tiles(const GlmArgs& a, const GlmPos& p, const SmLds& S,
-                                               const double (&x)[4]) {
-    const ModelArgs& M = a.m;
-    constexpr int SR = glm_row_stride(16);
-    constexpr int YO = glm_y_offset(16);
-    constexpr int kHalf = kSmXS / 2;
-    const int64_t ntiles = a.g.n_pad / 16;
-    const int d = a.s.d;
-    const int ti = threadIdx.x < kHalf ? (int)threadIdx.x : 0;
-    const bool tl = threadIdx.x < kHalf;
-    const double (*sptab)[10] = reinterpret_cast<const double (*)[10]>(S.sp);
-    // the A operands of M = invG_c X': invG_c[cl][4q + e], for the whole pass
-    double IA[16][4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const int k = 4 * p.q + e;
-        const bool ok = p.cl < d && k < d;
-        const f64x2* row = reinterpret_cast<const f64x2*>(S.W + 16 * (ok ? smm_symi(p.cl, k) : 0));
-#pragma unroll
-        for (int c2 = 0; c2 < 8; ++c2) {
-            const f64x2 v2 = row[c2];
-            IA[2 * c2][e] = ok ? v2.x : 0.0;
-            IA[2 * c2 + 1][e] = ok ? v2.y : 0.0;
-        }
-    }
-    pm_stage_first<LOGI>(a, S);
-    f64x4 U = f64x4{0.0, 0.0, 0.0, 0.0};
-    for (int64_t t = 0; t < ntiles; ++t) {
-        const int b = (int)(t & 1);
-        const double* LX = S.X + b * kSmXS;
-        const bool more = t + 1 < ntiles;
-        f64x2 nxt = f64x2{0.0, 0.0};
-        if (more) nxt = reinterpret_cast<const f64x2*>(M.X + (size_t)(t + 1) * kSmXS)[ti];
-        const double* xrow = LX + p.cl * SR + 4 * p.q;
-        f64x4 eta = f64x4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int slot = 0; slot < 4; ++slot)
-            eta = __builtin_amdgcn_mfma_f64_16x16x4f64(xrow[slot], x[slot], eta, 0, 0, 0);
-        double w[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int o = p.q + 4 * r;
-            const double wr = pm_dw<LOGI>(eta[r], LX[YO + o], sptab);
-            w[r] = t * 16 + o < M.n ? wr : 0.0;
-        }
-        // qf of (observation cl, chain c) -> vb[16 cl + c]
-        double xo[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) xo[r] = LX[p.cl * SR + p.q + 4 * r];
-#pragma unroll
-        for (int c = 0; c < 16; ++c) {
-            f64x4 Mq = f64x4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) Mq = __builtin_amdgcn_mfma_f64_16x16x4f64(IA[c][e], xrow[e], Mq, 0, 0, 0);
-            const double sq = ((Mq[0] * xo[0] + Mq[1] * xo[1]) + Mq[2] * xo[2]) + Mq[3] * xo[3];
-            const f64x4 Q = __builtin_amdgcn_mfma_f64_16x16x4f64(1.0, sq, f64x4{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
-            if ((c & 3) == p.q) S.vb[16 * p.cl + c] = Q[0];
-        }
-        smm_wave_sync();
-        double wq[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) wq[r] = w[r] * S.vb[16 * (p.q + 4 * r) + p.cl];
-        {
-            const double* gcol = LX + p.q * SR + 4 * (p.cl & 3) + (p.cl >> 2);
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk)
-                U = __builtin_amdgcn_mfma_f64_16x16x4f64(gcol[4 * kk * SR], wq[kk], U, 0, 0, 0);
-        }
-        smm_wave_sync();
-        if (more && tl) reinterpret_cast<f64x2*>(S.X + (b ^ 1) * kSmXS)[ti] = nxt;
-        __syncthreads();
-    }
-    return U;
-}
-
 // c = invG (X' (w o qf)) at x, invG in S.W; V: one of the tile's shared vectors
 __device__ __forceinline__ void pm_corr(const GlmArgs& a, const GlmPos& p, const SmLds& S, const double (&x)[4],
                                         double* V, double (&cv)[4]) {
-    const f64x4 U = a.m.kind == MK_LOGISTIC ? pm_corr_tiles<true>(a, p, S, x) : pm_corr_tiles<false>(a, p, S, x);
+    f64x4 U, U2;
+    if (a.m.kind == MK_LOGISTIC) smm_dw_tiles<true, true, false>(a, p, S, x, x, U, U2);
+    else smm_dw_tiles<false, true, false>(a, p, S, x, x, U, U2);
     const double u[4] = {U[0], U[1], U[2], U[3]};
     smm_put_vec(V, p, u);
     smm_wave_sync();

@@ -1,8 +1,10 @@
-// smm_device.hpp -- the device pieces the manifold samplers share (smmala.hip, pmala.hip): the LDS carve-up of a
+// smm_device.hpp -- the device pieces the manifold samplers share (smmala.hip, pmala.hip, rmhmc.hip): the LDS carve-up of a
 // workgroup of four 16-chain tiles, the pass over the observation tiles that forms the log-target, the gradient and the
 // metric tensor on fp64 MFMA (smm_tiles, smm_evalallt), and the small SPD algebra in the chain's four lanes (Cholesky
-// factor, inverse, matvec, quadratic form) with its load / store helpers.  The arithmetic of every piece is stated in
-// smmala.hip's header and DESIGN.md §4; tests/smmala_oracle.c restates every sum in the same order.
+// factor, inverse, solve, matvec, quadratic form) with its load / store helpers, and the second pass over the tiles with
+// the weight's derivative (smm_dw_tiles: PMALA's drift correction, RMHMC's two tensor terms).  The arithmetic of every
+// piece is stated in smmala.hip's and pmala.hip's headers and DESIGN.md §4; tests/smmala_oracle.c and its successors
+// restate every sum in the same order.
 #pragma once
 #include "glm_device.hpp"
 
@@ -283,6 +285,163 @@ __device__ __forceinline__ double smm_quad(const double* Mc, size_t ld, const do
         }
     }
     return part;
+}
+
+// ------------------------------------------------------------------ the tensor's derivatives (pmala.hip, rmhmc.hip)
+__device__ __forceinline__ double pm_probit_dw(double eta) {
+    const double la = det_normlogcdf(eta), lb = det_normlogcdf(-eta);
+    const double e2 = eta * eta;
+    const double A = (-(e2 + kLog2Pi)) / 2.0;
+    const double v01 = det_exp((((-e2) - 2.0 * la) - lb) - kLog2Pi);
+    return v01 * (det_exp(A - lb) - 2.0 * (det_exp(A) + eta * det_exp(la)));
+}
+
+// w = dv / d eta (pmala.hip's header).  y: the tile's response column (probit: unused; logistic: wt = s (2y - 1))
+template <bool LOGI>
+__device__ __forceinline__ double pm_dw(double eta, double y, const double (*sptab)[10]) {
+    if (LOGI) {
+        double term, rv;
+        det_logi(eta, y, term, rv, sptab);
+        const double sig = __builtin_fabs(rv);
+        const double v = sig * (1.0 - sig);
+        return (v * (1.0 - 2.0 * sig)) * (-y);
+    }
+    return pm_probit_dw(eta);
+}
+
+// first tile and the logistic term's table into LDS; every wave of the workgroup (two barriers)
+template <bool LOGI>
+__device__ __forceinline__ void pm_stage_first(const GlmArgs& a, const SmLds& S) {
+    constexpr int kHalf = kSmXS / 2;
+    const int ti = threadIdx.x < kHalf ? (int)threadIdx.x : 0;
+    __syncthreads();                                          // the previous pass's last tile has been read
+    {
+        const f64x2 v = reinterpret_cast<const f64x2*>(a.m.X)[ti];
+        if (threadIdx.x < kHalf) reinterpret_cast<f64x2*>(S.X)[ti] = v;
+    }
+    if (LOGI) {
+        for (int i = threadIdx.x; i < SP_NROWS * 10; i += 256) S.sp[i] = (&kSoftplusTab[0][0])[i];
+    }
+    __syncthreads();
+}
+
+// The second pass over the staged X tiles at the lane's coordinates x, with the weight's derivative w:
+//   QF: U  = X' (w o qf), qf_o = x_o' invG x_o, the chains' invG in the workspace S.W (pmala.hip's header: the sum over
+//       the slabs of dG_i invG[:, i], and trace(invG dG_r) in row r);
+//   T2: U2 = X' (w o t^2), t = X v by eta's MFMA chain with the lane's coordinates of v as the B operand (k-slice e, row
+//       q <-> coordinate 4q + e; v zero past d), the weight RN(w_o RN(t_o t_o)) (zero on padded observations), then the
+//       gradient's MFMA: an fma chain over the observations in ascending order from zero; row r is v' dG_r v.
+// Both read the same eta and w.  Returns at the lane's own coordinates.  Every wave of the workgroup calls it (barriers
+// inside; their number depends on the tile count alone).
+template <bool LOGI, bool QF, bool T2>
+__device__ __forceinline__ void smm_dw_tiles(const GlmArgs& a, const GlmPos& p, const SmLds& S, const double (&x)[4],
+                                             const double (&v)[4], f64x4& U, f64x4& U2) {
+    const ModelArgs& M = a.m;
+    constexpr int SR = glm_row_stride(16);
+    constexpr int YO = glm_y_offset(16);
+    constexpr int kHalf = kSmXS / 2;
+    const int64_t ntiles = a.g.n_pad / 16;
+    const int d = a.s.d;
+    const int ti = threadIdx.x < kHalf ? (int)threadIdx.x : 0;
+    const bool tl = threadIdx.x < kHalf;
+    const double (*sptab)[10] = reinterpret_cast<const double (*)[10]>(S.sp);
+    // the A operands of M = invG_c X': invG_c[cl][4q + e], for the whole pass
+    double IA[16][4];
+    if (QF) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int k = 4 * p.q + e;
+            const bool ok = p.cl < d && k < d;
+            const f64x2* row = reinterpret_cast<const f64x2*>(S.W + 16 * (ok ? smm_symi(p.cl, k) : 0));
+#pragma unroll
+            for (int c2 = 0; c2 < 8; ++c2) {
+                const f64x2 v2 = row[c2];
+                IA[2 * c2][e] = ok ? v2.x : 0.0;
+                IA[2 * c2 + 1][e] = ok ? v2.y : 0.0;
+            }
+        }
+    }
+    pm_stage_first<LOGI>(a, S);
+    U = f64x4{0.0, 0.0, 0.0, 0.0};
+    U2 = f64x4{0.0, 0.0, 0.0, 0.0};
+    for (int64_t t = 0; t < ntiles; ++t) {
+        const int b = (int)(t & 1);
+        const double* LX = S.X + b * kSmXS;
+        const bool more = t + 1 < ntiles;
+        f64x2 nxt = f64x2{0.0, 0.0};
+        if (more) nxt = reinterpret_cast<const f64x2*>(M.X + (size_t)(t + 1) * kSmXS)[ti];
+        const double* xrow = LX + p.cl * SR + 4 * p.q;
+        f64x4 eta = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int slot = 0; slot < 4; ++slot)
+            eta = __builtin_amdgcn_mfma_f64_16x16x4f64(xrow[slot], x[slot], eta, 0, 0, 0);
+        double w[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int o = p.q + 4 * r;
+            const double wr = pm_dw<LOGI>(eta[r], LX[YO + o], sptab);
+            w[r] = t * 16 + o < M.n ? wr : 0.0;
+        }
+        const double* gcol = LX + p.q * SR + 4 * (p.cl & 3) + (p.cl >> 2);
+        if (T2) {
+            f64x4 tt = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int slot = 0; slot < 4; ++slot)
+                tt = __builtin_amdgcn_mfma_f64_16x16x4f64(xrow[slot], v[slot], tt, 0, 0, 0);
+            double wt[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) wt[r] = w[r] * (tt[r] * tt[r]);
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk)
+                U2 = __builtin_amdgcn_mfma_f64_16x16x4f64(gcol[4 * kk * SR], wt[kk], U2, 0, 0, 0);
+        }
+        if (QF) {
+            // qf of (observation cl, chain c) -> vb[16 cl + c]
+            double xo[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) xo[r] = LX[p.cl * SR + p.q + 4 * r];
+#pragma unroll
+            for (int c = 0; c < 16; ++c) {
+                f64x4 Mq = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+                for (int e = 0; e < 4; ++e) Mq = __builtin_amdgcn_mfma_f64_16x16x4f64(IA[c][e], xrow[e], Mq, 0, 0, 0);
+                const double sq = ((Mq[0] * xo[0] + Mq[1] * xo[1]) + Mq[2] * xo[2]) + Mq[3] * xo[3];
+                const f64x4 Q = __builtin_amdgcn_mfma_f64_16x16x4f64(1.0, sq, f64x4{0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
+                if ((c & 3) == p.q) S.vb[16 * p.cl + c] = Q[0];
+            }
+            smm_wave_sync();
+            double wq[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) wq[r] = w[r] * S.vb[16 * (p.q + 4 * r) + p.cl];
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk)
+                U = __builtin_amdgcn_mfma_f64_16x16x4f64(gcol[4 * kk * SR], wq[kk], U, 0, 0, 0);
+        }
+        smm_wave_sync();
+        if (more && tl) reinterpret_cast<f64x2*>(S.X + (b ^ 1) * kSmXS)[ti] = nxt;
+        __syncthreads();
+    }
+}
+
+// (L L') \ b from the factor L in W: b in the tile's shared vector B [16 coords][16 chains] (Bc = B + cl); every lane
+// of the chain runs the whole substitution in its private LDS vector Yl (smm_inverse's chains with b for the unit
+// column: forward y[i] = (b[i] then fma(-L[i][k], y[k], .) over k = 0..i-1) / L[i][i]; backward from i = d-1:
+// x[i] = (y[i] then fma(-L[k][i], x[k], .) over k = i+1..d-1) / L[i][i]) and keeps its own coordinates.  B must not
+// overlap the lanes' private vectors.
+__device__ __forceinline__ void smm_solve(const double* Wc, const double* Bc, double* Yl, int d, int q,
+                                          double (&out)[4]) {
+    for (int i = 0; i < d; ++i) {
+        double t = Bc[16 * i];
+        for (int k = 0; k < i; ++k) t = __builtin_fma(-Wc[16 * smm_tri(i, k)], Yl[64 * k], t);
+        Yl[64 * i] = t / Wc[16 * smm_tri(i, i)];
+    }
+    for (int i = d - 1; i >= 0; --i) {
+        double t = Yl[64 * i];
+        for (int k = i + 1; k < d; ++k) t = __builtin_fma(-Wc[16 * smm_tri(k, i)], Yl[64 * k], t);
+        Yl[64 * i] = t / Wc[16 * smm_tri(i, i)];
+    }
+#pragma unroll
+    for (int e = 0; e < 4; ++e) out[e] = 4 * q + e < d ? Yl[64 * (4 * q + e)] : 0.0;
 }
 
 static hipError_t smm_lds_attr(const void* f) {

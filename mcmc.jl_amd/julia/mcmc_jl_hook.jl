@@ -138,7 +138,7 @@ function hipmodel(kind::Symbol; init::Vector{Float64}=Float64[], scale::Vector{F
                link_sign, X, Y, device)
 end
 
-# has_gradient of the descriptor: 0 eval only, 1 gradient, 2 gradient and tensor (SMMALA), 3 tensor derivatives too (PMALA)
+# has_gradient of the descriptor: 0 eval only, 1 gradient, 2 gradient and tensor (SMMALA), 3 tensor derivatives too (PMALA, RMHMC)
 hip_has_gradient(m::MCMCHipModel) = m.dtensor ? 3 : m.tensor ? 2 : m.gradient ? 1 : 0
 hastensor(m::MCMCHipModel) = m.tensor
 hasdtensor(m::MCMCHipModel) = m.dtensor
@@ -165,6 +165,10 @@ hip_sampler(s::SMMALA) = hip_cfg(7, 0., s.driftStep, 0, 0., 0., 0., 0., 0., 0., 
 # PMALA (MCMC_PMALA = 8): MALA's fields; the library needs a model created with has_gradient = 3 (tensor derivatives:
 # hipmodel(...; tensor=true, dtensor=true)), built for the probit and logistic catalogue models with d <= 16
 hip_sampler(s::PMALA) = hip_cfg(8, 0., s.driftStep, 0, 0., 0., 0., 0., 0., 0., hip_tuner(s.tuner), 0)
+# RMHMC (MCMC_RMHMC = 9): n_leaps = nLeaps, leap_step = leapStep, and nNewton in the t0 field (a double holding an
+# integer in 1 .. 2^31 - 1; the struct's size is fixed); PMALA's models (has_gradient = 3) with d <= 16; the tuner is
+# HMC's.  The library refuses RMHMC targets under SeqMC and storeLeaps
+hip_sampler(s::RMHMC) = hip_cfg(9, 0., 0., s.nLeaps, s.leapStep, 0., 0., 0., float64(s.nNewton), 0., hip_tuner(s.tuner), 0)
 hip_sampler(s::HMC) = hip_cfg(3, 0., 0., s.nLeaps, s.leapStep, 0., 0., 0., 0., 0., hip_tuner(s.tuner), 0)
 hip_sampler(s::HMCDA) = hip_cfg(4, 0., 0., 0, 0., s.rate, s.len, s.shrinkage, s.t0, s.step, hip_tuner(nothing), 0)
 hip_sampler(s::RAM) = hip_cfg(5, s.scale, 0., 0, 0., s.rate, 0., 0., 0., 0., hip_tuner(nothing), 0)
@@ -379,7 +383,7 @@ function hip_run_group(m::MCMCHipModel, s::MCMCSampler, r::SerialMC, n::Int, see
   end
 end
 
-has_grads(s::MCMCSampler) = isa(s, MALA) || isa(s, SMMALA) || isa(s, PMALA) || isa(s, HMC) || isa(s, HMCDA) || isa(s, NUTS)
+has_grads(s::MCMCSampler) = isa(s, MALA) || isa(s, SMMALA) || isa(s, PMALA) || isa(s, RMHMC) || isa(s, HMC) || isa(s, HMCDA) || isa(s, NUTS)
 # the sampler's own diagnostics of kept step j, chain c: {"accept"} for the Metropolis samplers, NUTS's
 # {"epsilon", "ndoublings"} (NUTS.jl:177, which has no "accept")
 function hip_step_diag(s::MCMCSampler, o::HipRun, j::Int, c::Int)

@@ -43,6 +43,7 @@ SAMPLER_RAM = 5
 SAMPLER_NUTS = 6
 SAMPLER_SMMALA = 7
 SAMPLER_PMALA = 8
+SAMPLER_RMHMC = 9
 
 VAR_IMSE = 1
 VAR_IPSE = 2

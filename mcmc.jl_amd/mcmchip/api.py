@@ -33,7 +33,7 @@ from ._lib import check, dptr
 __all__ = [
     "IsoNormalDot", "NormalDSL", "AbsNormalDSL", "DistDSL", "DistObsDSL", "LogisticRegression", "LinearRegression", "ProbitRegression", "vaso_data",
     "OrnsteinUhlenbeck", "ou_series", "MCMCLikelihoodModel", "model",
-    "RWM", "MALA", "SMMALA", "PMALA", "HMC", "HMCDA", "RAM", "NUTS", "EmpMCTuner", "EmpiricalMCMCTuner", "SerialMC", "MCMCTask", "MCMCChain",
+    "RWM", "MALA", "SMMALA", "PMALA", "RMHMC", "HMC", "HMCDA", "RAM", "NUTS", "EmpMCTuner", "EmpiricalMCMCTuner", "SerialMC", "MCMCTask", "MCMCChain",
     "run", "resume", "device_count",
 ]
 
@@ -492,6 +492,58 @@ class HMC(_Sampler):
     def cfg(self):
         c = super().cfg()
         c.n_leaps, c.leap_step = self.nLeaps, self.leapStep
+        return c
+
+
+class RMHMC(_Sampler):
+    """Riemannian manifold HMC (RMHMC.jl:28-48); positional forms as the reference's constructors, each with an
+    optional trailing tuner: RMHMC() = (6, 0.5, 4); RMHMC(nLeaps::Int) = (n, 3/n, 4); RMHMC(nLeaps::Int,
+    leapStep::Float64); RMHMC(nLeaps::Int, nNewton::Int) = (n, 3/n, nNewton); RMHMC(leapStep::Float64) =
+    (floor(3/leapStep), leapStep, 4); RMHMC(leapStep::Float64, nNewton::Int); RMHMC(nLeaps, leapStep, nNewton).  An int is
+    an Int and a float a Float64, as in Julia's dispatch.  Needs a model with tensor derivatives.  nNewton travels to
+    the library in the sampler cfg's t0."""
+    kind = _lib.SAMPLER_RMHMC
+    uses_tensor = True
+    uses_dtensor = True
+
+    def __init__(self, *args, tuner=None):
+        a = list(args)
+        if a and (a[-1] is None or isinstance(a[-1], EmpiricalMCMCTuner)):
+            tuner = a.pop()
+        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        is_flt = lambda v: isinstance(v, (float, np.floating))
+        if len(a) == 0:
+            n, e, k = 6, 0.5, 4                                                # RMHMC.jl:42
+        elif len(a) == 1 and is_int(a[0]):
+            n, e, k = int(a[0]), 3 / a[0] if a[0] else float("inf"), 4        # RMHMC.jl:43
+        elif len(a) == 1 and is_flt(a[0]):
+            n, e, k = self._leaps_of(a[0]), float(a[0]), 4                     # RMHMC.jl:46
+        elif len(a) == 2 and is_int(a[0]) and is_flt(a[1]):
+            n, e, k = int(a[0]), float(a[1]), 4                                # RMHMC.jl:44
+        elif len(a) == 2 and is_int(a[0]) and is_int(a[1]):
+            n, e, k = int(a[0]), 3 / a[0] if a[0] else float("inf"), int(a[1])   # RMHMC.jl:45
+        elif len(a) == 2 and is_flt(a[0]) and is_int(a[1]):
+            n, e, k = self._leaps_of(a[0]), float(a[0]), int(a[1])             # RMHMC.jl:47-48
+        elif len(a) == 3 and is_int(a[0]) and is_flt(a[1]) and is_int(a[2]):
+            n, e, k = int(a[0]), float(a[1]), int(a[2])                        # RMHMC.jl:34
+        else:
+            raise TypeError("RMHMC([nLeaps::Int][, leapStep::Float64][, nNewton::Int][, tuner])")
+        if not n > 0:
+            raise AssertionError("Number of leapfrog steps should be > 0")    # RMHMC.jl:35
+        if not e > 0:
+            raise AssertionError("Leapfrog step size should be > 0")          # RMHMC.jl:36
+        if not k > 0:
+            raise AssertionError("Number of Newton steps should be > 0")      # RMHMC.jl:37
+        self.nLeaps, self.leapStep, self.nNewton, self.tuner = n, e, k, tuner
+
+    @staticmethod
+    def _leaps_of(leapStep: float) -> int:
+        """int(floor(3 / leapStep)) (RMHMC.jl:46); a step that is not positive fails the step's assert instead"""
+        return int(np.floor(3 / leapStep)) if leapStep > 0 and np.isfinite(3 / leapStep) else 1
+
+    def cfg(self):
+        c = super().cfg()
+        c.n_leaps, c.leap_step, c.t0 = self.nLeaps, self.leapStep, float(self.nNewton)
         return c
 
 
