@@ -95,7 +95,7 @@ enum {
 
 /* samplers */
 enum { MCMC_RWM = 1, MCMC_MALA = 2, MCMC_HMC = 3, MCMC_HMCDA = 4, MCMC_RAM = 5, MCMC_NUTS = 6, MCMC_SMMALA = 7,
-       MCMC_PMALA = 8, MCMC_RMHMC = 9 };
+       MCMC_PMALA = 8, MCMC_RMHMC = 9, MCMC_ERMLMC = 10, MCMC_RMLMC = 11 };
 
 typedef struct mcmc_ctx mcmc_ctx;
 typedef struct mcmc_model mcmc_model;
@@ -131,17 +131,20 @@ typedef struct {
 
 typedef struct {
     int32_t kind;            /* MCMC_RWM | MCMC_MALA | MCMC_HMC | MCMC_HMCDA | MCMC_RAM | MCMC_NUTS | MCMC_SMMALA |
-                                MCMC_PMALA | MCMC_RMHMC                                           */
+                                MCMC_PMALA | MCMC_RMHMC | MCMC_ERMLMC | MCMC_RMLMC                */
     double scale;            /* RWM, RAM: scale (RWM.jl:25, RAM.jl:23)                             */
     double drift_step;       /* MALA: driftStep (MALA.jl:51); SMMALA: driftStep (SMMALA.jl:24);
                                 PMALA: driftStep (PMALA.jl:26)                                    */
     int64_t n_leaps;         /* HMC: nLeaps (HMC.jl:54); NUTS: maxdoublings (NUTS.jl:31);
-                                RMHMC: nLeaps (RMHMC.jl:29), at most 2^20                          */
-    double leap_step;        /* HMC: leapStep (HMC.jl:55); RMHMC: leapStep (RMHMC.jl:30)           */
+                                RMHMC: nLeaps (RMHMC.jl:29), at most 2^20; ERMLMC, RMLMC: nLeaps
+                                (ERMLMC.jl:26, RMLMC.jl:27), at most 2^20                          */
+    double leap_step;        /* HMC: leapStep (HMC.jl:55); RMHMC: leapStep (RMHMC.jl:30); ERMLMC, RMLMC:
+                                leapStep (ERMLMC.jl:27, RMLMC.jl:28)                               */
     double rate, len, shrinkage, t0, step;   /* HMCDA (HMCDA.jl:25-29); rate: RAM target rate (RAM.jl:24);
                                 t0: RMHMC's nNewton (RMHMC.jl:31), a double holding an integer in 1 .. 2^31 - 1
+                                t0: RMLMC's nNewton (RMLMC.jl:29) likewise; ERMLMC does not read it
                                 (the struct's size is fixed; any other value answers MCMC_E_INVALID_ARG)  */
-    int32_t tuner;           /* 0: nothing; 1: EmpiricalMCMCTuner (MALA, HMC, SMMALA, PMALA, RMHMC) */
+    int32_t tuner;           /* 0: nothing; 1: EmpiricalMCMCTuner (MALA, HMC, SMMALA, PMALA, RMHMC, ERMLMC, RMLMC) */
     int64_t adapt_step, max_step;            /* EmpMCTuner (samplers.jl:33-37)                      */
     double target_path, target_rate;
     int64_t max_leaps;       /* HMCDA/HMC-tuner safety cap on leapfrogs per step (0 -> 1<<20)      */
@@ -241,7 +244,24 @@ int mcmc_runner_validate(const mcmc_runner_cfg* cfg);
  * log-target that is not finite, a Cholesky pivot <= 0 or not finite at any G, or a position or ratio that is not
  * finite is rejected (the reference would throw out of chol), and so is a step whose nRandomLeaps draw is 0 (the
  * reference leaves proposedGrad undefined there).  mcmc_run_seqmc and mcmc_chains_store_leaps answer
- * MCMC_E_UNSUPPORTED for RMHMC chains. */
+ * MCMC_E_UNSUPPORTED for RMHMC chains.
+ * ERMLMC (ERMLMC.jl:84-179, MCMC_ERMLMC = 10) and RMLMC (RMLMC.jl:89-179, MCMC_RMLMC = 11): RMHMC's models and sizes
+ * (has_gradient == 3, d <= 16; otherwise MCMC_E_NEEDS_GRADIENT with "ERMLMC / RMLMC sampler requires model with
+ * gradient function" / "... tensor function" / "... function of tensor derivatives", or MCMC_E_UNSUPPORTED for
+ * d > 16).  n_leaps = nLeaps, leap_step = leapStep, RMLMC: t0 = nNewton; the tuner is HMC's EmpiricalHMCTune.  The
+ * state is x, lp and the gradient; every step recomputes G, cholG, invG, traceInvGxdG and dphi at the state's position
+ * and draws velocity = chol(invG)' randn and nRandomLeaps = ceil(rand() nLeaps) (there is no timeStep).  The tensor
+ * C = 0.5 (permutedims(dG, [3 2 1]) + permutedims(dG, [1 3 2]) - dG) is never formed: on these models dG is symmetric
+ * in its three indices, so vxC(v) = 0.5 X' diag(w o X v) X, one weighted Gram pass over X.  The energies are the
+ * reference's as written: ERMLMC's carries -sum(log(diag(cholG))), RMLMC's +sum(log(diag(cholG))).  The evaluation
+ * count is the sum of nRandomLeaps.  Departures: a step whose trajectory meets a log-target that is not finite, a
+ * Cholesky pivot <= 0 or not finite at any G, invG or G +- c vxC (the reference's logdet throws on a negative
+ * determinant and goes through LU on an indefinite matrix with a positive one), or a position, velocity or ratio that
+ * is not finite is rejected, and so is a step whose nRandomLeaps draw is 0 (the reference would read an undefined
+ * proposedLogTarget).  mcmc_chains_set_state re-evaluates at the new position and the next step recomputes all geometry
+ * from it; the reference's reset hooks (ERMLMC.jl:64-67, RMLMC.jl:69-72) leave invG, cholG, traceInvGxdG, dphi and C at
+ * the previous position, which is why mcmc_run_seqmc answers MCMC_E_UNSUPPORTED for these targets;
+ * mcmc_chains_store_leaps does too. */
 int mcmc_chains_create(mcmc_model* model, const mcmc_sampler_cfg* sampler, int64_t nchains,
                        int64_t chain_offset, uint64_t seed, const double* init_x, mcmc_chains** out);
 int mcmc_chains_destroy(mcmc_chains* chains);
@@ -260,13 +280,13 @@ int mcmc_chains_fork(mcmc_chains* src, int64_t first, int64_t count, mcmc_chains
 /* steps consumed so far (the sampler's own loop counter i). */
 int mcmc_chains_steps_done(mcmc_chains* chains, int64_t* steps);
 /* per-chain adaptive state after the last run, [nchains] each (any may be NULL): step = the current step size
- * (MALA / SMMALA / PMALA driftStep under EmpiricalMALATune, HMC / RMHMC leapStep under EmpiricalHMCTune, HMCDA leapStep, HMCDA.jl:136,140);
- * step_bar = HMCDA's dual-averaged dualLeapStep (HMCDA.jl:138); nleaps = the tuned HMC / RMHMC nLeaps (HMC.jl:42).
+ * (MALA / SMMALA / PMALA driftStep under EmpiricalMALATune, HMC / RMHMC / ERMLMC / RMLMC leapStep under EmpiricalHMCTune, HMCDA leapStep, HMCDA.jl:136,140);
+ * step_bar = HMCDA's dual-averaged dualLeapStep (HMCDA.jl:138); nleaps = the tuned HMC / RMHMC / ERMLMC / RMLMC nLeaps (HMC.jl:42).
  * NUTS: step = epsilon, step_bar = exp(log epsilon_bar) (NUTS.jl:169-172).
  * A quantity the sampler does not adapt reads NaN (steps) or 0 (nleaps). */
 int mcmc_chains_tuner_state(mcmc_chains* chains, double* step, double* step_bar, int32_t* nleaps);
 /* log-target evaluations (with gradient for MALA/HMC/HMCDA) summed over all chains since
- * create/reset: steps x C for RWM/MALA, the leapfrog count for HMC/HMCDA (HMC.jl:93-102) and RMHMC (the sum of nRandomLeaps),
+ * create/reset: steps x C for RWM/MALA, the leapfrog count for HMC/HMCDA (HMC.jl:93-102) and RMHMC, ERMLMC, RMLMC (the sum of nRandomLeaps),
  * whose trajectory length varies per chain under HMCDA / EmpMCTuner; NUTS: the leapfrogs of every tree and of
  * the initial epsilon search. */
 int mcmc_chains_evals(mcmc_chains* chains, int64_t* evals);

@@ -14,7 +14,7 @@ enum DistKind : int32_t {
     DK_CAUCHY = 8, DK_LOGNORMAL = 9, DK_LAPLACE = 10
 };
 enum SamplerKind : int32_t { SK_RWM = 1, SK_MALA = 2, SK_HMC = 3, SK_HMCDA = 4, SK_RAM = 5, SK_NUTS = 6, SK_SMMALA = 7,
-                            SK_PMALA = 8, SK_RMHMC = 9 };
+                            SK_PMALA = 8, SK_RMHMC = 9, SK_ERMLMC = 10, SK_RMLMC = 11 };
 
 // Model parameters as the kernels see them (device pointers).
 struct ModelArgs {
@@ -39,13 +39,13 @@ struct SamplerArgs {
     int32_t tuner;              // EmpMCTuner on/off
     double scale;               // RWM
     double drift_step;          // MALA
-    int64_t n_leaps;            // HMC, RMHMC; NUTS: maxdoublings
-    double leap_step;           // HMC, RMHMC
+    int64_t n_leaps;            // HMC, RMHMC, ERMLMC, RMLMC; NUTS: maxdoublings
+    double leap_step;           // HMC, RMHMC, ERMLMC, RMLMC
     double rate, len, shrinkage, t0, step;  // HMCDA
     int64_t adapt_step, max_step;
     double target_path, target_rate;
     int64_t max_leaps;
-    int32_t n_newton;           // RMHMC: fixed-point passes of the momentum and of the position
+    int32_t n_newton;           // RMHMC: fixed-point passes of the momentum and of the position; RMLMC: of the velocity
 };
 
 // Per-chain sampler state (SoA, length ld).  Which arrays are live depends on the sampler.
@@ -57,7 +57,7 @@ struct ChainState {
     double* t_bar;              // HMCDA dualLeapStep | NUTS log epsilon_bar (lebar)
     double* t_h;                // HMCDA dualH | NUTS hbar
     double* t_mu;               // NUTS mu = log(10 epsilon_0) (NUTS.jl:128)
-    int32_t* t_leaps;           // HMC / RMHMC tuned nLeaps
+    int32_t* t_leaps;           // HMC / RMHMC / ERMLMC / RMLMC tuned nLeaps
     int32_t* t_acc;             // tuner accepted counter
     int32_t* t_prop;            // tuner proposed counter
     double* mom;                // regression HMC / HMCDA on d-slices (d > 128): the momentum parked in HBM across each
@@ -73,7 +73,8 @@ struct ChainState {
     double* sm_invG;
     double* sm_ft;
     double* sm_pG;              // SMMALA: the proposal's tensor and inverse (dead between steps); RMHMC keeps
-                                //   sm_pinvG alone, the trajectory's current inverse (dead between steps)
+                                //   sm_pinvG alone, the trajectory's current inverse (dead between steps); ERMLMC and
+                                //   RMLMC keep both, the trajectory's current tensor and inverse (lmc.hip)
     double* sm_pinvG;
     double* pm_c;               // PMALA: the drift correction c = sum_i invG dG_i invG[:, i] at x [d][ld]; PMALA keeps
                                 //   SMMALA's five arrays too

@@ -25,7 +25,7 @@
 namespace mcmc {
 
 // TAG_NUTS_DOUBLING / TAG_NUTS_MERGE: the direction, accept and merge draws of a NUTS step (nuts.hpp)
-enum : uint32_t { TAG_NORMAL = 0u, TAG_ACCEPT = 1u, TAG_NUTS_DOUBLING = 3u, TAG_NUTS_MERGE = 4u, TAG_RMHMC = 5u, TAG_DATA = 7u };
+enum : uint32_t { TAG_NORMAL = 0u, TAG_ACCEPT = 1u, TAG_NUTS_DOUBLING = 3u, TAG_NUTS_MERGE = 4u, TAG_RMHMC = 5u, TAG_LMC = 6u, TAG_DATA = 7u };
 
 struct u32x4 { uint32_t x, y, z, w; };
 

@@ -62,6 +62,9 @@ hipError_t mcmc_launch_pmala_corr(const mcmc::KernelArgs& a, hipStream_t st);
 hipError_t mcmc_launch_pmala_step(const mcmc::KernelArgs& a, hipStream_t st);
 // RMHMC on the same models and sizes (rmhmc.hip): the state is x, lp and g; st.sm_pinvG is its workspace
 hipError_t mcmc_launch_rmhmc_step(const mcmc::KernelArgs& a, hipStream_t st);
+// ERMLMC and RMLMC on the same models and sizes (lmc.hip): the state is x, lp and g; st.sm_pG and st.sm_pinvG are the
+// trajectory's workspace
+hipError_t mcmc_launch_lmc_step(const mcmc::KernelArgs& a, hipStream_t st);
 // RAM on regression targets, 32 < d <= 1024 (glm_ram_wave.hip): per step the eval kernel and the accept / factor-update
 // kernel; u [C][ustride], nz [C], xprop [d][ld], lpp [C] are the device buffers between them.  st2 (may be null):
 // a second stream on which half of a large batch runs, forked from and joined back to st by the two events

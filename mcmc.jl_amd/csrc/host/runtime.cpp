@@ -269,6 +269,20 @@ extern "C" int mcmc_sampler_validate(const mcmc_sampler_cfg* s) {
             if (s->n_leaps > ((int64_t)1 << 20))
                 return fail(MCMC_E_UNSUPPORTED, "RMHMC is built for nLeaps <= 2^20");
             break;
+        case MCMC_ERMLMC:
+        case MCMC_RMLMC: {
+            const bool semi = s->kind == MCMC_RMLMC;
+            if (!(s->n_leaps > 0)) return fail(MCMC_E_INVALID_ARG, "Number of leapfrog steps should be > 0");   // ERMLMC.jl:31
+            if (!(s->leap_step > 0)) return fail(MCMC_E_INVALID_ARG, "Leapfrog step size should be > 0");       // ERMLMC.jl:32
+            if (semi) {
+                if (!(s->t0 > 0)) return fail(MCMC_E_INVALID_ARG, "Number of Newton steps should be > 0");      // RMLMC.jl:35
+                if (!(s->t0 <= 2147483647.0) || s->t0 != (double)(int64_t)s->t0)
+                    return fail(MCMC_E_INVALID_ARG, "RMLMC: t0 carries nNewton and should hold an integer in 1 .. 2^31 - 1");
+            }
+            if (s->n_leaps > ((int64_t)1 << 20))
+                return fail(MCMC_E_UNSUPPORTED, std::string(semi ? "RMLMC" : "ERMLMC") + " is built for nLeaps <= 2^20");
+            break;
+        }
         case MCMC_RAM: {
             if (!(s->scale > 0)) return fail(MCMC_E_INVALID_ARG, "scale should be > 0");               // RAM.jl:27
             if (!(s->rate > 0.0 && s->rate < 1.0)) {
@@ -757,6 +771,9 @@ extern "C" int mcmc_model_eval_dtensor(mcmc_model* m, int64_t nchains, const dou
 
 // ------------------------------------------------------------------ chains
 static bool is_manifold(int32_t kind) { return kind == SK_SMMALA || kind == SK_PMALA; }
+static bool is_lmc(int32_t kind) { return kind == SK_ERMLMC || kind == SK_RMLMC; }
+// the trajectory samplers on the metric tensor: the state is x, lp and g, the tuner EmpiricalHMCTune
+static bool is_rm_family(int32_t kind) { return kind == SK_RMHMC || is_lmc(kind); }
 
 static void free_state(mcmc_chains* c) {
     ChainState& s = c->st;
@@ -778,6 +795,7 @@ static hipError_t launch_chain_step(const mcmc_chains* c, const KernelArgs& a, h
     if (c->sa.kind == SK_SMMALA) return mcmc_launch_smmala_step(a, st);
     if (c->sa.kind == SK_PMALA) return mcmc_launch_pmala_step(a, st);
     if (c->sa.kind == SK_RMHMC) return mcmc_launch_rmhmc_step(a, st);
+    if (is_lmc(c->sa.kind)) return mcmc_launch_lmc_step(a, st);
     return launch_step(c->layout, a, st);
 }
 
@@ -878,7 +896,7 @@ static int init_state(mcmc_chains* c) {
         HIP_TRY(launch_eval(c->layout, a, c->st.x, c->st.lp, c->st.g, 1, st));
     }
     if ((sa.kind == SK_MALA || is_manifold(sa.kind)) && sa.tuner) HIP_TRY(mcmc_fill_f64(c->st.t_step, c->C, sa.drift_step, st));
-    if ((sa.kind == SK_HMC || sa.kind == SK_RMHMC) && sa.tuner) {   // EmpiricalHMCTune(nLeaps, leapStep, 0, 0)
+    if ((sa.kind == SK_HMC || is_rm_family(sa.kind)) && sa.tuner) {   // EmpiricalHMCTune(nLeaps, leapStep, 0, 0)
         HIP_TRY(mcmc_fill_f64(c->st.t_step, c->C, sa.leap_step, st));
         HIP_TRY(mcmc_fill_i32(c->st.t_leaps, c->C, (int32_t)sa.n_leaps, st));
     }
@@ -937,7 +955,8 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
                                         " (the d x d jump factor of every chain is kept in HBM)");
     if (s->kind != MCMC_RWM && s->kind != MCMC_RAM && !m->has_gradient) {
         const char* nm = s->kind == MCMC_MALA ? "MALA" : s->kind == MCMC_HMC ? "HMC" : s->kind == MCMC_NUTS ? "NUTS"
-                         : s->kind == MCMC_SMMALA ? "SMMALA" : s->kind == MCMC_PMALA ? "PMALA" : s->kind == MCMC_RMHMC ? "RMHMC" : "HMCDA";
+                         : s->kind == MCMC_SMMALA ? "SMMALA" : s->kind == MCMC_PMALA ? "PMALA" : s->kind == MCMC_RMHMC ? "RMHMC"
+                         : s->kind == MCMC_ERMLMC ? "ERMLMC" : s->kind == MCMC_RMLMC ? "RMLMC" : "HMCDA";
         return fail(MCMC_E_NEEDS_GRADIENT, std::string(nm) + " sampler requires model with gradient function");
     }
     if (s->kind == MCMC_SMMALA && m->has_gradient < 2)                                                   // SMMALA.jl:51
@@ -950,6 +969,11 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
         return fail(MCMC_E_NEEDS_GRADIENT, "RMHMC sampler requires model with tensor function");
     if (s->kind == MCMC_RMHMC && m->has_gradient < 3)                                                    // RMHMC.jl:66
         return fail(MCMC_E_NEEDS_GRADIENT, "RMHMC sampler requires model with function of tensor derivatives");
+    if (is_lmc(s->kind) && m->has_gradient < 3) {                                                        // ERMLMC.jl:60-61, RMLMC.jl:65-66
+        const std::string nm = s->kind == MCMC_ERMLMC ? "ERMLMC" : "RMLMC";
+        return fail(MCMC_E_NEEDS_GRADIENT, nm + (m->has_gradient < 2 ? " sampler requires model with tensor function"
+                                                                      : " sampler requires model with function of tensor derivatives"));
+    }
     mcmc_ctx* ctx = m->ctx;
     if (int r = set_device(ctx)) return r;
     const int d = m->args.d;
@@ -965,6 +989,11 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
                                             "registers); d = " + std::to_string(d));
     if (s->kind == MCMC_RMHMC && d > mcmc_smmala_max_d())
         return fail(MCMC_E_UNSUPPORTED, "RMHMC is built for d <= " + std::to_string(mcmc_smmala_max_d()) +
+                                            " (SMMALA's geometry: the metric tensor of a 16-chain tile is held in "
+                                            "registers); d = " + std::to_string(d));
+    if (is_lmc(s->kind) && d > mcmc_smmala_max_d())
+        return fail(MCMC_E_UNSUPPORTED, std::string(s->kind == MCMC_ERMLMC ? "ERMLMC" : "RMLMC") + " is built for d <= " +
+                                            std::to_string(mcmc_smmala_max_d()) +
                                             " (SMMALA's geometry: the metric tensor of a 16-chain tile is held in "
                                             "registers); d = " + std::to_string(d));
     if (s->kind == MCMC_NUTS) {
@@ -1002,7 +1031,7 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
     sa.target_path = s->target_path;
     sa.target_rate = s->target_rate;
     sa.max_leaps = s->max_leaps > 0 ? s->max_leaps : (int64_t)1 << 20;
-    sa.n_newton = s->kind == MCMC_RMHMC ? (int32_t)s->t0 : 0;
+    sa.n_newton = s->kind == MCMC_RMHMC || s->kind == MCMC_RMLMC ? (int32_t)s->t0 : 0;
     auto bail = [&](int code) {
         mcmc_chains_destroy(c);
         return code;
@@ -1015,7 +1044,7 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
     if (c->layout == LAYOUT_GLM && d > 128 && (sa.kind == SK_HMC || sa.kind == SK_HMCDA))   // d-sliced: momentum
         if (int r = dmalloc(&c->st.mom, (size_t)mcmc_glm_d_pad(d) * c->ld)) return bail(r);      // parking (glm_hmc)
     if (int r = dmalloc(&c->st.lp, nc)) return bail(r);
-    const bool tuned = sa.tuner && (sa.kind == SK_MALA || sa.kind == SK_HMC || sa.kind == SK_RMHMC || is_manifold(sa.kind));
+    const bool tuned = sa.tuner && (sa.kind == SK_MALA || sa.kind == SK_HMC || is_rm_family(sa.kind) || is_manifold(sa.kind));
     if (is_manifold(sa.kind)) {
         const size_t nr = (size_t)d * (size_t)(d + 1) / 2 * (size_t)c->ld;
         if (int r = dmalloc(&c->st.sm_G, nr)) return bail(r);
@@ -1026,8 +1055,10 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
         if (sa.kind == SK_PMALA)
             if (int r = dmalloc(&c->st.pm_c, nst)) return bail(r);
     }
-    if (sa.kind == SK_RMHMC)                     // the trajectory's current inverse (rmhmc.hip; dead between steps)
+    if (is_rm_family(sa.kind))                   // the trajectory's current inverse (rmhmc.hip; dead between steps)
         if (int r = dmalloc(&c->st.sm_pinvG, (size_t)d * (size_t)(d + 1) / 2 * (size_t)c->ld)) return bail(r);
+    if (is_lmc(sa.kind))                         // and its current tensor (lmc.hip; dead between steps)
+        if (int r = dmalloc(&c->st.sm_pG, (size_t)d * (size_t)(d + 1) / 2 * (size_t)c->ld)) return bail(r);
     if (tuned || sa.kind == SK_HMCDA || sa.kind == SK_NUTS)
         if (int r = dmalloc(&c->st.t_step, nc)) return bail(r);
     if (sa.kind == SK_NUTS) {
@@ -1043,7 +1074,7 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
         if (int r = dmalloc(&c->st.t_h, nc)) return bail(r);
     }
     if (tuned) {
-        if (sa.kind == SK_HMC || sa.kind == SK_RMHMC)
+        if (sa.kind == SK_HMC || is_rm_family(sa.kind))
             if (int r = dmalloc(&c->st.t_leaps, nc)) return bail(r);
         if (int r = dmalloc(&c->st.t_acc, nc)) return bail(r);
         if (int r = dmalloc(&c->st.t_prop, nc)) return bail(r);
@@ -1452,6 +1483,10 @@ extern "C" int mcmc_chains_store_leaps(mcmc_chains* c, int64_t cap, double* pars
     if (c->sa.kind == SK_RMHMC)
         return fail(MCMC_E_UNSUPPORTED, "storeLeaps is not built for RMHMC: the reference's RMHMC keeps no leapfrog "
                                         "record (RMHMC.jl:120-155)");
+    if (is_lmc(c->sa.kind))
+        return fail(MCMC_E_UNSUPPORTED, std::string("storeLeaps is not built for ") +
+                                            (c->sa.kind == SK_ERMLMC ? "ERMLMC" : "RMLMC") +
+                                            ": the reference's sampler keeps no leapfrog record (ERMLMC.jl:114-152)");
     if (c->sa.kind != SK_HMC && c->sa.kind != SK_HMCDA)
         return fail(MCMC_E_INVALID_ARG, "storeLeaps needs an HMC or HMCDA sampler");
     if (cap < 0 || !grads || !mom || !lp || !H || !nleaps) return fail(MCMC_E_INVALID_ARG, "bad storeLeaps buffers");
@@ -1775,6 +1810,12 @@ extern "C" int mcmc_run_seqmc(mcmc_chains* const* targets, int32_t ntargets, int
         if (targets[t]->sa.kind == SK_RMHMC)
             return fail(MCMC_E_UNSUPPORTED, "SeqMC does not run RMHMC targets: the population runner's device path is "
                                             "built for the samplers without a metric tensor");
+        if (is_lmc(targets[t]->sa.kind))
+            return fail(MCMC_E_UNSUPPORTED, std::string("SeqMC does not run ") +
+                                                (targets[t]->sa.kind == SK_ERMLMC ? "ERMLMC" : "RMLMC") +
+                                                " targets: the sampler's reset hook keeps invG, cholG, traceInvGxdG, dphi "
+                                                "and C of the chain's previous position (ERMLMC.jl:64-67), which "
+                                                "mcmc_chains_set_state does not");
         if (targets[t]->sa.kind == SK_SMMALA)
             return fail(MCMC_E_UNSUPPORTED, "SeqMC does not run SMMALA targets: the sampler's reset hook keeps invG and "
                                             "firstTerm of the chain's previous position (SMMALA.jl:54-57)");

@@ -43,38 +43,6 @@ namespace mcmc {
 // log 2 and log pi, the nearest doubles (RMHMC.jl:107)
 constexpr double kRmLog2 = 0x1.62e42fefa39efp-1;
 constexpr double kRmLogPi = 0x1.250d048e7a1bdp+0;
-// smm_device.hpp's carve-up, then the leapfrog count's maximum
-constexpr int kRmLdsDoubles = kSmLdsDoubles + 2;
-
-// workgroup-wide max of the live chains' leapfrog counts (0 when none is live): every wave must reach it
-__device__ __forceinline__ int rm_max(int* iscr, int v, bool live) {
-    __syncthreads();
-    if (threadIdx.x == 0) iscr[0] = 0;
-    __syncthreads();
-    if (live) atomicMax(&iscr[0], v);
-    __syncthreads();
-    const int r = iscr[0];
-    __syncthreads();
-    return r;
-}
-
-// out = M in, M the chain's symmetric packed matrix in W, through the tile's shared vector V
-__device__ __forceinline__ void rm_symv(const GlmPos& p, const double* Wc, double* V, int d, const double (&in)[4],
-                                        double (&out)[4]) {
-    smm_put_vec(V, p, in);
-    smm_wave_sync();
-    smm_symv(Wc, V + p.cl, d, p.q, out);
-    smm_wave_sync();
-}
-
-// the lane's partial of a' b over its coordinates
-__device__ __forceinline__ double rm_dot_part(const GlmPos& p, int d, const double (&u)[4], const double (&v)[4]) {
-    double part = 0.0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-        if (4 * p.q + e < d) part = __builtin_fma(u[e], v[e], part);
-    return part;
-}
 
 template <bool QF, bool T2>
 __device__ __forceinline__ void rm_pass(const GlmArgs& a, const GlmPos& p, const SmLds& S, const double (&x)[4],

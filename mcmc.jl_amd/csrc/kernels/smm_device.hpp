@@ -1,4 +1,4 @@
-// smm_device.hpp -- the device pieces the manifold samplers share (smmala.hip, pmala.hip, rmhmc.hip): the LDS carve-up of a
+// smm_device.hpp -- the device pieces the manifold samplers share (smmala.hip, pmala.hip, rmhmc.hip, lmc.hip): the LDS carve-up of a
 // workgroup of four 16-chain tiles, the pass over the observation tiles that forms the log-target, the gradient and the
 // metric tensor on fp64 MFMA (smm_tiles, smm_evalallt), and the small SPD algebra in the chain's four lanes (Cholesky
 // factor, inverse, solve, matvec, quadratic form) with its load / store helpers, and the second pass over the tiles with
@@ -61,6 +61,25 @@ __device__ __forceinline__ void smm_probit_obs(double eta, double y, double& ter
     const double A = (-(eta * eta + kLog2Pi)) / 2.0;
     w = y * det_exp(A - la) - (1.0 - y) * det_exp(A - lb);
     v = det_exp(((-(eta * eta) - la) - lb) - kLog2Pi);
+}
+
+// X' diag(weights) X of one staged tile added to the tile's sixteen accumulators T (chain c: rows q + 4r, column cl):
+// the weights of (observation q + 4r, chain cl) in vb[64 r + lane]; per k-slice, chain c: A = X[obs 4kk + q][cl],
+// B = v_c[obs 4kk + q] X[obs 4kk + q][cl]
+__device__ __forceinline__ void smm_gram_mfma(const double* LX, const SmLds& S, const GlmPos& p, f64x4 (&T)[16]) {
+    typedef double f64x2_t __attribute__((ext_vector_type(2)));
+    constexpr int SR = glm_row_stride(16);
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+        const double xa = LX[(4 * kk + p.q) * SR + p.cl];
+        const f64x2_t* vrow = reinterpret_cast<const f64x2_t*>(S.vb + 64 * kk + 16 * p.q);
+#pragma unroll
+        for (int c2 = 0; c2 < 8; ++c2) {
+            const f64x2_t v2 = vrow[c2];
+            T[2 * c2] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa, v2.x * xa, T[2 * c2], 0, 0, 0);
+            T[2 * c2 + 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa, v2.y * xa, T[2 * c2 + 1], 0, 0, 0);
+        }
+    }
 }
 
 // One pass over the observation tiles: the likelihood partial of the lane, the gradient accumulator G (own
@@ -146,18 +165,7 @@ __device__ __forceinline__ double smm_tiles(const GlmArgs& a, const GlmPos& p, c
                 G = __builtin_amdgcn_mfma_f64_16x16x4f64(gcol[4 * kk * SR], rv[kk], G, 0, 0, 0);
         }
         smm_wave_sync();
-        // the tensor: per k-slice, chain c: A = X[obs 4kk + q][cl], B = v_c[obs 4kk + q] X[obs 4kk + q][cl]
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const double xa = LX[(4 * kk + p.q) * SR + p.cl];
-            const f64x2_t* vrow = reinterpret_cast<const f64x2_t*>(S.vb + 64 * kk + 16 * p.q);
-#pragma unroll
-            for (int c2 = 0; c2 < 8; ++c2) {
-                const f64x2_t v2 = vrow[c2];
-                T[2 * c2] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa, v2.x * xa, T[2 * c2], 0, 0, 0);
-                T[2 * c2 + 1] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa, v2.y * xa, T[2 * c2 + 1], 0, 0, 0);
-            }
-        }
+        smm_gram_mfma(LX, S, p, T);
         smm_wave_sync();
         if (more && tl) reinterpret_cast<f64x2_t*>(S.X + (b ^ 1) * kSmXS)[ti] = nxt;
         __syncthreads();
@@ -333,9 +341,14 @@ __device__ __forceinline__ void pm_stage_first(const GlmArgs& a, const SmLds& S)
 //       gradient's MFMA: an fma chain over the observations in ascending order from zero; row r is v' dG_r v.
 // Both read the same eta and w.  Returns at the lane's own coordinates.  Every wave of the workgroup calls it (barriers
 // inside; their number depends on the tile count alone).
-template <bool LOGI, bool QF, bool T2>
-__device__ __forceinline__ void smm_dw_tiles(const GlmArgs& a, const GlmPos& p, const SmLds& S, const double (&x)[4],
-                                             const double (&v)[4], f64x4& U, f64x4& U2) {
+//   GR: T += X' diag(w o t) X of the tile's sixteen chains, the tensor pass's accumulators and MFMA path
+//       (smm_gram_mfma) with the weight RN(w_o t_o) (zero on padded observations): lmc.hip's K(v), 2 vxC(v).  Not
+//       with QF: both use the wave's weight rows.
+template <bool LOGI, bool QF, bool T2, bool GR>
+__device__ __forceinline__ void smm_dw_tiles_impl(const GlmArgs& a, const GlmPos& p, const SmLds& S,
+                                                  const double (&x)[4], const double (&v)[4], f64x4& U, f64x4& U2,
+                                                  f64x4 (&T)[16]) {
+    static_assert(!(QF && GR), "QF and GR share the wave's weight rows");
     const ModelArgs& M = a.m;
     constexpr int SR = glm_row_stride(16);
     constexpr int YO = glm_y_offset(16);
@@ -364,6 +377,10 @@ __device__ __forceinline__ void smm_dw_tiles(const GlmArgs& a, const GlmPos& p, 
     pm_stage_first<LOGI>(a, S);
     U = f64x4{0.0, 0.0, 0.0, 0.0};
     U2 = f64x4{0.0, 0.0, 0.0, 0.0};
+    if (GR) {
+#pragma unroll
+        for (int c = 0; c < 16; ++c) T[c] = f64x4{0.0, 0.0, 0.0, 0.0};
+    }
     for (int64_t t = 0; t < ntiles; ++t) {
         const int b = (int)(t & 1);
         const double* LX = S.X + b * kSmXS;
@@ -383,11 +400,19 @@ __device__ __forceinline__ void smm_dw_tiles(const GlmArgs& a, const GlmPos& p, 
             w[r] = t * 16 + o < M.n ? wr : 0.0;
         }
         const double* gcol = LX + p.q * SR + 4 * (p.cl & 3) + (p.cl >> 2);
-        if (T2) {
-            f64x4 tt = f64x4{0.0, 0.0, 0.0, 0.0};
+        f64x4 tt = f64x4{0.0, 0.0, 0.0, 0.0};
+        if (T2 || GR) {
 #pragma unroll
             for (int slot = 0; slot < 4; ++slot)
                 tt = __builtin_amdgcn_mfma_f64_16x16x4f64(xrow[slot], v[slot], tt, 0, 0, 0);
+        }
+        if (GR) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) S.vb[64 * r + p.lane] = w[r] * tt[r];
+            smm_wave_sync();
+            smm_gram_mfma(LX, S, p, T);
+        }
+        if (T2) {
             double wt[4];
 #pragma unroll
             for (int r = 0; r < 4; ++r) wt[r] = w[r] * (tt[r] * tt[r]);
@@ -423,6 +448,26 @@ __device__ __forceinline__ void smm_dw_tiles(const GlmArgs& a, const GlmPos& p, 
     }
 }
 
+template <bool LOGI, bool QF, bool T2>
+__device__ __forceinline__ void smm_dw_tiles(const GlmArgs& a, const GlmPos& p, const SmLds& S, const double (&x)[4],
+                                             const double (&v)[4], f64x4& U, f64x4& U2) {
+    f64x4 T[16];
+    smm_dw_tiles_impl<LOGI, QF, T2, false>(a, p, S, x, v, U, U2, T);
+}
+
+// the tile's sixteen accumulators -> the workspace S.W (lower triangles), as smm_evalallt lays the tensor out
+__device__ __forceinline__ void smm_put_tiles(const GlmPos& p, const SmLds& S, int d, const f64x4 (&T)[16]) {
+#pragma unroll
+    for (int c = 0; c < 16; ++c) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ar = p.q + 4 * r;
+            if (ar < d && p.cl <= ar) S.W[16 * smm_tri(ar, p.cl) + c] = T[c][r];
+        }
+    }
+    smm_wave_sync();
+}
+
 // (L L') \ b from the factor L in W: b in the tile's shared vector B [16 coords][16 chains] (Bc = B + cl); every lane
 // of the chain runs the whole substitution in its private LDS vector Yl (smm_inverse's chains with b for the unit
 // column: forward y[i] = (b[i] then fma(-L[i][k], y[k], .) over k = 0..i-1) / L[i][i]; backward from i = d-1:
@@ -442,6 +487,40 @@ __device__ __forceinline__ void smm_solve(const double* Wc, const double* Bc, do
     }
 #pragma unroll
     for (int e = 0; e < 4; ++e) out[e] = 4 * q + e < d ? Yl[64 * (4 * q + e)] : 0.0;
+}
+
+// ------------------------------------------------------------------ the trajectory samplers (rmhmc.hip, lmc.hip)
+// smm_device.hpp's carve-up, then the leapfrog count's maximum
+constexpr int kRmLdsDoubles = kSmLdsDoubles + 2;
+
+// workgroup-wide max of the live chains' leapfrog counts (0 when none is live): every wave must reach it
+__device__ __forceinline__ int rm_max(int* iscr, int v, bool live) {
+    __syncthreads();
+    if (threadIdx.x == 0) iscr[0] = 0;
+    __syncthreads();
+    if (live) atomicMax(&iscr[0], v);
+    __syncthreads();
+    const int r = iscr[0];
+    __syncthreads();
+    return r;
+}
+
+// out = M in, M the chain's symmetric packed matrix in W, through the tile's shared vector V
+__device__ __forceinline__ void rm_symv(const GlmPos& p, const double* Wc, double* V, int d, const double (&in)[4],
+                                        double (&out)[4]) {
+    smm_put_vec(V, p, in);
+    smm_wave_sync();
+    smm_symv(Wc, V + p.cl, d, p.q, out);
+    smm_wave_sync();
+}
+
+// the lane's partial of a' b over its coordinates
+__device__ __forceinline__ double rm_dot_part(const GlmPos& p, int d, const double (&u)[4], const double (&v)[4]) {
+    double part = 0.0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (4 * p.q + e < d) part = __builtin_fma(u[e], v[e], part);
+    return part;
 }
 
 static hipError_t smm_lds_attr(const void* f) {

@@ -29,6 +29,8 @@ const RWM_K, MALA_K, HMC_K, HMCDA_K, RAM_K = 1, 2, 3, 4, 5
 const SMMALA_K = 7            # MCMC_SMMALA: needs a model with has_gradient = 2 (gradient and metric tensor)
 const PMALA_K = 8             # MCMC_PMALA: needs a model with has_gradient = 3 (gradient, tensor and tensor derivatives)
 const RMHMC_K = 9             # MCMC_RMHMC: PMALA's models, d <= 16; nNewton travels in the cfg's t0 field
+const ERMLMC_K = 10           # MCMC_ERMLMC: RMHMC's models, d <= 16; not a SeqMC target
+const RMLMC_K = 11            # MCMC_RMLMC: likewise; nNewton travels in the cfg's t0 field
 
 check(st) = st == 0 ? nothing :
     error(unsafe_string(ccall((:mcmc_last_error, lib), Cstring, ())))   # reference @assert text
@@ -77,6 +79,9 @@ hmcda(; rate=0.65, len=2., shrinkage=0.05, t0=10., step=0.75) =
     SamplerCfg(HMCDA_K, 0, 0, 0, 0, rate, len, shrinkage, t0, step, 0, 0, 0, 0, 0, 0)
 # RMHMC.jl:42: nNewton in the t0 field, a double holding an integer
 rmhmc(n = 6, eps = 0.5, newton = 4) = SamplerCfg(RMHMC_K, 0, 0, n, eps, 0, 0, 0, Float64(newton), 0, 0, 0, 0, 0, 0, 0)
+# ERMLMC.jl:37, RMLMC.jl:40
+ermlmc(n = 10, eps = 0.1) = SamplerCfg(ERMLMC_K, 0, 0, n, eps, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+rmlmc(n = 6, eps = 0.5, newton = 4) = SamplerCfg(RMLMC_K, 0, 0, n, eps, 0, 0, 0, Float64(newton), 0, 0, 0, 0, 0, 0, 0)
 ram(scale = 1.0, rate = 0.234) = SamplerCfg(RAM_K, scale, 0, 0, 0, rate, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)   # RAM.jl:22-34
 
 function chains(model, s::SamplerCfg, nchains; seed = 1, offset = 0)

@@ -138,7 +138,7 @@ function hipmodel(kind::Symbol; init::Vector{Float64}=Float64[], scale::Vector{F
                link_sign, X, Y, device)
 end
 
-# has_gradient of the descriptor: 0 eval only, 1 gradient, 2 gradient and tensor (SMMALA), 3 tensor derivatives too (PMALA, RMHMC)
+# has_gradient of the descriptor: 0 eval only, 1 gradient, 2 gradient and tensor (SMMALA), 3 tensor derivatives too (PMALA, RMHMC, ERMLMC, RMLMC)
 hip_has_gradient(m::MCMCHipModel) = m.dtensor ? 3 : m.tensor ? 2 : m.gradient ? 1 : 0
 hastensor(m::MCMCHipModel) = m.tensor
 hasdtensor(m::MCMCHipModel) = m.dtensor
@@ -169,6 +169,11 @@ hip_sampler(s::PMALA) = hip_cfg(8, 0., s.driftStep, 0, 0., 0., 0., 0., 0., 0., h
 # integer in 1 .. 2^31 - 1; the struct's size is fixed); PMALA's models (has_gradient = 3) with d <= 16; the tuner is
 # HMC's.  The library refuses RMHMC targets under SeqMC and storeLeaps
 hip_sampler(s::RMHMC) = hip_cfg(9, 0., 0., s.nLeaps, s.leapStep, 0., 0., 0., float64(s.nNewton), 0., hip_tuner(s.tuner), 0)
+# ERMLMC (MCMC_ERMLMC = 10) and RMLMC (MCMC_RMLMC = 11): n_leaps = nLeaps, leap_step = leapStep, RMLMC's nNewton in the
+# t0 field as RMHMC's; RMHMC's models (has_gradient = 3) with d <= 16; the tuner is HMC's.  The library refuses these
+# targets under SeqMC (its set_state recomputes all geometry, the reference's reset hooks do not) and storeLeaps
+hip_sampler(s::ERMLMC) = hip_cfg(10, 0., 0., s.nLeaps, s.leapStep, 0., 0., 0., 0., 0., hip_tuner(s.tuner), 0)
+hip_sampler(s::RMLMC) = hip_cfg(11, 0., 0., s.nLeaps, s.leapStep, 0., 0., 0., float64(s.nNewton), 0., hip_tuner(s.tuner), 0)
 hip_sampler(s::HMC) = hip_cfg(3, 0., 0., s.nLeaps, s.leapStep, 0., 0., 0., 0., 0., hip_tuner(s.tuner), 0)
 hip_sampler(s::HMCDA) = hip_cfg(4, 0., 0., 0, 0., s.rate, s.len, s.shrinkage, s.t0, s.step, hip_tuner(nothing), 0)
 hip_sampler(s::RAM) = hip_cfg(5, s.scale, 0., 0, 0., s.rate, 0., 0., 0., 0., hip_tuner(nothing), 0)
@@ -180,6 +185,9 @@ hip_is_nuts(s::MCMCSampler) = isa(s, NUTS)
 # SeqMC: NUTS adapts epsilon by its own step counter, so its targets stay on the reference path
 hip_seqmc_able(s::MCMCSampler) = true
 hip_seqmc_able(s::NUTS) = false
+# ERMLMC and RMLMC: mcmc_run_seqmc refuses them (their set_state departs from the reset hooks), so they stay there too
+hip_seqmc_able(s::ERMLMC) = false
+hip_seqmc_able(s::RMLMC) = false
 
 # storeLeaps (HMC.jl:145-150, HMCDA.jl:110-117): leapfrog states recorded per step, up to a cap -- the trajectory
 # length for HMC (the tuner's maxStep bound when tuned), hip_leap_cap for HMCDA, whose length round(len / leapStep)
@@ -383,7 +391,7 @@ function hip_run_group(m::MCMCHipModel, s::MCMCSampler, r::SerialMC, n::Int, see
   end
 end
 
-has_grads(s::MCMCSampler) = isa(s, MALA) || isa(s, SMMALA) || isa(s, PMALA) || isa(s, RMHMC) || isa(s, HMC) || isa(s, HMCDA) || isa(s, NUTS)
+has_grads(s::MCMCSampler) = isa(s, MALA) || isa(s, SMMALA) || isa(s, PMALA) || isa(s, RMHMC) || isa(s, ERMLMC) || isa(s, RMLMC) || isa(s, HMC) || isa(s, HMCDA) || isa(s, NUTS)
 # the sampler's own diagnostics of kept step j, chain c: {"accept"} for the Metropolis samplers, NUTS's
 # {"epsilon", "ndoublings"} (NUTS.jl:177, which has no "accept")
 function hip_step_diag(s::MCMCSampler, o::HipRun, j::Int, c::Int)

@@ -8,7 +8,7 @@ from .api import (  # noqa: F401
     IsoNormalDot, NormalDSL, AbsNormalDSL, DistDSL, DistObsDSL, LogisticRegression, LinearRegression, ProbitRegression, vaso_data,
     OrnsteinUhlenbeck, ou_series,
     MCMCLikelihoodModel, model,
-    RWM, MALA, SMMALA, PMALA, RMHMC, HMC, HMCDA, RAM, NUTS, EmpMCTuner, EmpiricalMCMCTuner, SerialMC, MCMCTask, MCMCChain,
+    RWM, MALA, SMMALA, PMALA, RMHMC, ERMLMC, RMLMC, HMC, HMCDA, RAM, NUTS, EmpMCTuner, EmpiricalMCMCTuner, SerialMC, MCMCTask, MCMCChain,
     run, prun, resume, reset, srand, drawn_key, device_count,
 )
 from .seqmc import SeqMC, SeqMCChain, run_seqmc, resume_seqmc  # noqa: F401

@@ -44,6 +44,8 @@ SAMPLER_NUTS = 6
 SAMPLER_SMMALA = 7
 SAMPLER_PMALA = 8
 SAMPLER_RMHMC = 9
+SAMPLER_ERMLMC = 10
+SAMPLER_RMLMC = 11
 
 VAR_IMSE = 1
 VAR_IPSE = 2

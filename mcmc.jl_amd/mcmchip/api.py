@@ -33,7 +33,7 @@ from ._lib import check, dptr
 __all__ = [
     "IsoNormalDot", "NormalDSL", "AbsNormalDSL", "DistDSL", "DistObsDSL", "LogisticRegression", "LinearRegression", "ProbitRegression", "vaso_data",
     "OrnsteinUhlenbeck", "ou_series", "MCMCLikelihoodModel", "model",
-    "RWM", "MALA", "SMMALA", "PMALA", "RMHMC", "HMC", "HMCDA", "RAM", "NUTS", "EmpMCTuner", "EmpiricalMCMCTuner", "SerialMC", "MCMCTask", "MCMCChain",
+    "RWM", "MALA", "SMMALA", "PMALA", "RMHMC", "ERMLMC", "RMLMC", "HMC", "HMCDA", "RAM", "NUTS", "EmpMCTuner", "EmpiricalMCMCTuner", "SerialMC", "MCMCTask", "MCMCChain",
     "run", "resume", "device_count",
 ]
 
@@ -544,6 +544,69 @@ class RMHMC(_Sampler):
     def cfg(self):
         c = super().cfg()
         c.n_leaps, c.leap_step, c.t0 = self.nLeaps, self.leapStep, float(self.nNewton)
+        return c
+
+
+class RMLMC(RMHMC):
+    """Semi-explicit Riemannian manifold Lagrangian Monte Carlo (RMLMC.jl:26-46): RMHMC's constructor forms (RMLMC() =
+    (6, 0.5, 4); RMLMC(nLeaps::Int) = (n, 3/n, 4); RMLMC(leapStep::Float64) = (floor(3/leapStep), leapStep, 4); ...),
+    each with an optional trailing tuner.  Needs a model with tensor derivatives.  nNewton travels to the library in
+    the sampler cfg's t0."""
+    kind = _lib.SAMPLER_RMLMC
+
+    def __init__(self, *args, tuner=None):
+        try:
+            super().__init__(*args, tuner=tuner)
+        except TypeError:
+            raise TypeError("RMLMC([nLeaps::Int][, leapStep::Float64][, nNewton::Int][, tuner])") from None
+
+
+class ERMLMC(_Sampler):
+    """Explicit Riemannian manifold Lagrangian Monte Carlo (ERMLMC.jl:25-41); positional forms as the reference's
+    constructors: ERMLMC(i::Int = 10, s::Float64 = 0.1); ERMLMC(s::Float64[, tuner]) = (10, s); ERMLMC(i::Int, tuner) =
+    (i, 0.1); ERMLMC(tuner) = (10, 0.1); ERMLMC(i, s, tuner); keywords init, scale, tuner.  An int is an Int and a float
+    a Float64, as in Julia's dispatch.  Needs a model with tensor derivatives."""
+    kind = _lib.SAMPLER_ERMLMC
+    uses_tensor = True
+    uses_dtensor = True
+
+    def __init__(self, *args, init: Optional[int] = None, scale: Optional[float] = None, tuner=None):
+        a = list(args)
+        is_int = lambda v: isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+        is_flt = lambda v: isinstance(v, (float, np.floating))
+        is_tn = lambda v: v is None or isinstance(v, EmpiricalMCMCTuner)
+        kw = init is not None or scale is not None or tuner is not None
+        if a and kw:
+            raise TypeError("ERMLMC: positional forms or the keywords init, scale, tuner")
+        if len(a) == 0:
+            n, e = (10 if init is None else init), (0.1 if scale is None else scale)   # ERMLMC.jl:37, 41
+            if not is_int(n) or not is_flt(e):
+                raise TypeError("ERMLMC(;init::Int, scale::Float64, tuner)")
+        elif len(a) == 1 and is_int(a[0]):
+            n, e = int(a[0]), 0.1                                              # ERMLMC.jl:37
+        elif len(a) == 1 and is_flt(a[0]):
+            n, e = 10, float(a[0])                                             # ERMLMC.jl:38
+        elif len(a) == 1 and isinstance(a[0], EmpiricalMCMCTuner):
+            n, e, tuner = 10, 0.1, a[0]                                        # ERMLMC.jl:40
+        elif len(a) == 2 and is_int(a[0]) and is_flt(a[1]):
+            n, e = int(a[0]), float(a[1])                                      # ERMLMC.jl:37
+        elif len(a) == 2 and is_flt(a[0]) and is_tn(a[1]):
+            n, e, tuner = 10, float(a[0]), a[1]                                # ERMLMC.jl:38
+        elif len(a) == 2 and is_int(a[0]) and isinstance(a[1], EmpiricalMCMCTuner):
+            n, e, tuner = int(a[0]), 0.1, a[1]                                 # ERMLMC.jl:39
+        elif len(a) == 3 and is_int(a[0]) and is_flt(a[1]) and is_tn(a[2]):
+            n, e, tuner = int(a[0]), float(a[1]), a[2]                         # ERMLMC.jl:30
+        else:
+            raise TypeError("ERMLMC([nLeaps::Int][, leapStep::Float64][, tuner])")
+        if not n > 0:
+            raise AssertionError("Number of leapfrog steps should be > 0")    # ERMLMC.jl:31
+        if not e > 0:
+            raise AssertionError("Leapfrog step size should be > 0")          # ERMLMC.jl:32
+        self.nLeaps, self.leapStep, self.tuner = int(n), float(e), tuner
+
+    def cfg(self):
+        c = super().cfg()
+        c.n_leaps, c.leap_step = self.nLeaps, self.leapStep
         return c
 
 
