@@ -239,50 +239,64 @@ extern "C" int mcmc_ctx_synchronize(mcmc_ctx* ctx) {
 
 // ------------------------------------------------------------------ validation
 
+// What validation and chain creation ask about a sampler kind
+struct SamplerInfo {
+    const char* name;
+    int needs;              // the model's has_gradient level: 0 none, 1 gradient, 2 tensor, 3 tensor derivatives
+    bool newton_in_t0;      // t0 carries nNewton, a double holding an integer
+    const char* d_reason;   // non-NULL: built for d <= mcmc_smmala_max_d(), and why
+};
+
+static SamplerInfo sampler_info(int32_t kind) {
+    static const char* const tile = " (the metric tensor of a 16-chain tile is held in registers); d = ";
+    static const char* const smm_tile =
+        " (SMMALA's geometry: the metric tensor of a 16-chain tile is held in registers); d = ";
+    switch (kind) {
+        case MCMC_RWM: return {"RWM", 0, false, nullptr};
+        case MCMC_RAM: return {"RAM", 0, false, nullptr};
+        case MCMC_MALA: return {"MALA", 1, false, nullptr};
+        case MCMC_HMC: return {"HMC", 1, false, nullptr};
+        case MCMC_NUTS: return {"NUTS", 1, false, nullptr};
+        case MCMC_SMMALA: return {"SMMALA", 2, false, tile};          // SMMALA.jl:51
+        case MCMC_PMALA: return {"PMALA", 3, false, smm_tile};        // PMALA.jl:54-55
+        case MCMC_RMHMC: return {"RMHMC", 3, true, smm_tile};         // RMHMC.jl:65-66
+        case MCMC_ERMLMC: return {"ERMLMC", 3, false, smm_tile};      // ERMLMC.jl:60-61
+        case MCMC_RMLMC: return {"RMLMC", 3, true, smm_tile};         // RMLMC.jl:65-66
+        default: return {"HMCDA", 1, false, nullptr};
+    }
+}
+
 extern "C" int mcmc_sampler_validate(const mcmc_sampler_cfg* s) {
     if (!s) return fail(MCMC_E_INVALID_ARG, "sampler cfg is NULL");
+    const SamplerInfo si = sampler_info(s->kind);
     switch (s->kind) {
         case MCMC_RWM:
             if (!(s->scale > 0)) return fail(MCMC_E_INVALID_ARG, "scale should be > 0");               // RWM.jl:29
             if (s->tuner) return fail(MCMC_E_UNSUPPORTED, "RWM has no tuner in the reference (RWMTuner is abstract)");
             break;
         case MCMC_MALA:
-            if (!(s->drift_step > 0)) return fail(MCMC_E_INVALID_ARG, "MALA drift step should be > 0"); // MALA.jl:55
-            break;
         case MCMC_SMMALA:
-            if (!(s->drift_step > 0)) return fail(MCMC_E_INVALID_ARG, "SMMALA drift step should be > 0"); // SMMALA.jl:27
-            break;
-        case MCMC_PMALA:
-            if (!(s->drift_step > 0)) return fail(MCMC_E_INVALID_ARG, "PMALA drift step should be > 0"); // PMALA.jl:30
+        case MCMC_PMALA:                                             // MALA.jl:55, SMMALA.jl:27, PMALA.jl:30
+            if (!(s->drift_step > 0)) return fail(MCMC_E_INVALID_ARG, std::string(si.name) + " drift step should be > 0");
             break;
         case MCMC_HMC:
             if (!(s->n_leaps > 0)) return fail(MCMC_E_INVALID_ARG, "inner steps should be > 0");        // HMC.jl:60
             if (!(s->leap_step > 0)) return fail(MCMC_E_INVALID_ARG, "inner steps scaling should be > 0"); // HMC.jl:61
             break;
         case MCMC_RMHMC:
-            if (!(s->n_leaps > 0)) return fail(MCMC_E_INVALID_ARG, "Number of leapfrog steps should be > 0");   // RMHMC.jl:35
-            if (!(s->leap_step > 0)) return fail(MCMC_E_INVALID_ARG, "Leapfrog step size should be > 0");       // RMHMC.jl:36
-            if (!(s->t0 > 0)) return fail(MCMC_E_INVALID_ARG, "Number of Newton steps should be > 0");          // RMHMC.jl:37
-            // nNewton travels in t0, a double holding an integer
-            if (!(s->t0 <= 2147483647.0) || s->t0 != (double)(int64_t)s->t0)
-                return fail(MCMC_E_INVALID_ARG, "RMHMC: t0 carries nNewton and should hold an integer in 1 .. 2^31 - 1");
-            if (s->n_leaps > ((int64_t)1 << 20))
-                return fail(MCMC_E_UNSUPPORTED, "RMHMC is built for nLeaps <= 2^20");
-            break;
         case MCMC_ERMLMC:
-        case MCMC_RMLMC: {
-            const bool semi = s->kind == MCMC_RMLMC;
-            if (!(s->n_leaps > 0)) return fail(MCMC_E_INVALID_ARG, "Number of leapfrog steps should be > 0");   // ERMLMC.jl:31
-            if (!(s->leap_step > 0)) return fail(MCMC_E_INVALID_ARG, "Leapfrog step size should be > 0");       // ERMLMC.jl:32
-            if (semi) {
-                if (!(s->t0 > 0)) return fail(MCMC_E_INVALID_ARG, "Number of Newton steps should be > 0");      // RMLMC.jl:35
+        case MCMC_RMLMC:                                             // RMHMC.jl:35-37, ERMLMC.jl:31-32, RMLMC.jl:35
+            if (!(s->n_leaps > 0)) return fail(MCMC_E_INVALID_ARG, "Number of leapfrog steps should be > 0");
+            if (!(s->leap_step > 0)) return fail(MCMC_E_INVALID_ARG, "Leapfrog step size should be > 0");
+            if (si.newton_in_t0) {
+                if (!(s->t0 > 0)) return fail(MCMC_E_INVALID_ARG, "Number of Newton steps should be > 0");
                 if (!(s->t0 <= 2147483647.0) || s->t0 != (double)(int64_t)s->t0)
-                    return fail(MCMC_E_INVALID_ARG, "RMLMC: t0 carries nNewton and should hold an integer in 1 .. 2^31 - 1");
+                    return fail(MCMC_E_INVALID_ARG, std::string(si.name) +
+                                                        ": t0 carries nNewton and should hold an integer in 1 .. 2^31 - 1");
             }
             if (s->n_leaps > ((int64_t)1 << 20))
-                return fail(MCMC_E_UNSUPPORTED, std::string(semi ? "RMLMC" : "ERMLMC") + " is built for nLeaps <= 2^20");
+                return fail(MCMC_E_UNSUPPORTED, std::string(si.name) + " is built for nLeaps <= 2^20");
             break;
-        }
         case MCMC_RAM: {
             if (!(s->scale > 0)) return fail(MCMC_E_INVALID_ARG, "scale should be > 0");               // RAM.jl:27
             if (!(s->rate > 0.0 && s->rate < 1.0)) {
@@ -953,49 +967,20 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
     if (s->kind == MCMC_RAM && m->args.d > mcmc_wpc_ram_max_d())
         return fail(MCMC_E_UNSUPPORTED, "RAM is built for d <= " + std::to_string(mcmc_wpc_ram_max_d()) +
                                         " (the d x d jump factor of every chain is kept in HBM)");
-    if (s->kind != MCMC_RWM && s->kind != MCMC_RAM && !m->has_gradient) {
-        const char* nm = s->kind == MCMC_MALA ? "MALA" : s->kind == MCMC_HMC ? "HMC" : s->kind == MCMC_NUTS ? "NUTS"
-                         : s->kind == MCMC_SMMALA ? "SMMALA" : s->kind == MCMC_PMALA ? "PMALA" : s->kind == MCMC_RMHMC ? "RMHMC"
-                         : s->kind == MCMC_ERMLMC ? "ERMLMC" : s->kind == MCMC_RMLMC ? "RMLMC" : "HMCDA";
-        return fail(MCMC_E_NEEDS_GRADIENT, std::string(nm) + " sampler requires model with gradient function");
-    }
-    if (s->kind == MCMC_SMMALA && m->has_gradient < 2)                                                   // SMMALA.jl:51
-        return fail(MCMC_E_NEEDS_GRADIENT, "SMMALA sampler requires model with tensor function");
-    if (s->kind == MCMC_PMALA && m->has_gradient < 2)                                                    // PMALA.jl:54
-        return fail(MCMC_E_NEEDS_GRADIENT, "PMALA sampler requires model with tensor function");
-    if (s->kind == MCMC_PMALA && m->has_gradient < 3)                                                    // PMALA.jl:55
-        return fail(MCMC_E_NEEDS_GRADIENT, "PMALA sampler requires model with function of tensor derivatives");
-    if (s->kind == MCMC_RMHMC && m->has_gradient < 2)                                                    // RMHMC.jl:65
-        return fail(MCMC_E_NEEDS_GRADIENT, "RMHMC sampler requires model with tensor function");
-    if (s->kind == MCMC_RMHMC && m->has_gradient < 3)                                                    // RMHMC.jl:66
-        return fail(MCMC_E_NEEDS_GRADIENT, "RMHMC sampler requires model with function of tensor derivatives");
-    if (is_lmc(s->kind) && m->has_gradient < 3) {                                                        // ERMLMC.jl:60-61, RMLMC.jl:65-66
-        const std::string nm = s->kind == MCMC_ERMLMC ? "ERMLMC" : "RMLMC";
-        return fail(MCMC_E_NEEDS_GRADIENT, nm + (m->has_gradient < 2 ? " sampler requires model with tensor function"
-                                                                      : " sampler requires model with function of tensor derivatives"));
-    }
+    const SamplerInfo si = sampler_info(s->kind);
+    const std::string needs = std::string(si.name) + " sampler requires model with ";
+    if (si.needs >= 1 && !m->has_gradient) return fail(MCMC_E_NEEDS_GRADIENT, needs + "gradient function");
+    if (si.needs >= 2 && m->has_gradient < 2) return fail(MCMC_E_NEEDS_GRADIENT, needs + "tensor function");
+    if (si.needs >= 3 && m->has_gradient < 3)
+        return fail(MCMC_E_NEEDS_GRADIENT, needs + "function of tensor derivatives");
     mcmc_ctx* ctx = m->ctx;
     if (int r = set_device(ctx)) return r;
     const int d = m->args.d;
     if (model_is_separable(m) && d > mcmc_wpc_max_d())
         return fail(MCMC_E_UNSUPPORTED, "separable targets support d <= 16384");
-    if (s->kind == MCMC_SMMALA && d > mcmc_smmala_max_d())
-        return fail(MCMC_E_UNSUPPORTED, "SMMALA is built for d <= " + std::to_string(mcmc_smmala_max_d()) +
-                                            " (the metric tensor of a 16-chain tile is held in registers); d = " +
-                                            std::to_string(d));
-    if (s->kind == MCMC_PMALA && d > mcmc_smmala_max_d())
-        return fail(MCMC_E_UNSUPPORTED, "PMALA is built for d <= " + std::to_string(mcmc_smmala_max_d()) +
-                                            " (SMMALA's geometry: the metric tensor of a 16-chain tile is held in "
-                                            "registers); d = " + std::to_string(d));
-    if (s->kind == MCMC_RMHMC && d > mcmc_smmala_max_d())
-        return fail(MCMC_E_UNSUPPORTED, "RMHMC is built for d <= " + std::to_string(mcmc_smmala_max_d()) +
-                                            " (SMMALA's geometry: the metric tensor of a 16-chain tile is held in "
-                                            "registers); d = " + std::to_string(d));
-    if (is_lmc(s->kind) && d > mcmc_smmala_max_d())
-        return fail(MCMC_E_UNSUPPORTED, std::string(s->kind == MCMC_ERMLMC ? "ERMLMC" : "RMLMC") + " is built for d <= " +
-                                            std::to_string(mcmc_smmala_max_d()) +
-                                            " (SMMALA's geometry: the metric tensor of a 16-chain tile is held in "
-                                            "registers); d = " + std::to_string(d));
+    if (si.d_reason && d > mcmc_smmala_max_d())
+        return fail(MCMC_E_UNSUPPORTED, std::string(si.name) + " is built for d <= " +
+                                            std::to_string(mcmc_smmala_max_d()) + si.d_reason + std::to_string(d));
     if (s->kind == MCMC_NUTS) {
         if (model_is_glm(m))
             return fail(MCMC_E_UNSUPPORTED, "NUTS is not built for the regression models (built: the separable and joint "
@@ -1031,7 +1016,7 @@ extern "C" int mcmc_chains_create(mcmc_model* m, const mcmc_sampler_cfg* s, int6
     sa.target_path = s->target_path;
     sa.target_rate = s->target_rate;
     sa.max_leaps = s->max_leaps > 0 ? s->max_leaps : (int64_t)1 << 20;
-    sa.n_newton = s->kind == MCMC_RMHMC || s->kind == MCMC_RMLMC ? (int32_t)s->t0 : 0;
+    sa.n_newton = si.newton_in_t0 ? (int32_t)s->t0 : 0;
     auto bail = [&](int code) {
         mcmc_chains_destroy(c);
         return code;
@@ -1484,8 +1469,7 @@ extern "C" int mcmc_chains_store_leaps(mcmc_chains* c, int64_t cap, double* pars
         return fail(MCMC_E_UNSUPPORTED, "storeLeaps is not built for RMHMC: the reference's RMHMC keeps no leapfrog "
                                         "record (RMHMC.jl:120-155)");
     if (is_lmc(c->sa.kind))
-        return fail(MCMC_E_UNSUPPORTED, std::string("storeLeaps is not built for ") +
-                                            (c->sa.kind == SK_ERMLMC ? "ERMLMC" : "RMLMC") +
+        return fail(MCMC_E_UNSUPPORTED, std::string("storeLeaps is not built for ") + sampler_info(c->sa.kind).name +
                                             ": the reference's sampler keeps no leapfrog record (ERMLMC.jl:114-152)");
     if (c->sa.kind != SK_HMC && c->sa.kind != SK_HMCDA)
         return fail(MCMC_E_INVALID_ARG, "storeLeaps needs an HMC or HMCDA sampler");
@@ -1811,8 +1795,7 @@ extern "C" int mcmc_run_seqmc(mcmc_chains* const* targets, int32_t ntargets, int
             return fail(MCMC_E_UNSUPPORTED, "SeqMC does not run RMHMC targets: the population runner's device path is "
                                             "built for the samplers without a metric tensor");
         if (is_lmc(targets[t]->sa.kind))
-            return fail(MCMC_E_UNSUPPORTED, std::string("SeqMC does not run ") +
-                                                (targets[t]->sa.kind == SK_ERMLMC ? "ERMLMC" : "RMLMC") +
+            return fail(MCMC_E_UNSUPPORTED, std::string("SeqMC does not run ") + sampler_info(targets[t]->sa.kind).name +
                                                 " targets: the sampler's reset hook keeps invG, cholG, traceInvGxdG, dphi "
                                                 "and C of the chain's previous position (ERMLMC.jl:64-67), which "
                                                 "mcmc_chains_set_state does not");

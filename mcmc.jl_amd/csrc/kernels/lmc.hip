@@ -3,11 +3,11 @@
 // (src/samplers/RMLMC.jl:89-179, lmc_step<true>), statement by statement.
 //
 // Geometry, log-target, gradient, tensor and the small algebra are smmala.hip's (smm_device.hpp); the barrier
-// discipline is rmhmc.hip's.
+// discipline and the step's frame (tuner registers, leapfrog count, mask, commit) are rmhmc.hip's.
 //
 // Neither sampler forms C = 0.5 (permutedims(dG, [3 2 1]) + permutedims(dG, [1 3 2]) - dG).  On these models
 // dG[a, b, r] = sum_o w_o X_oa X_ob X_or is symmetric in all three indices, so C = 0.5 dG and
-//   vxC(v)   = 0.5 K(v),  K(v) = X' diag(w o t) X,  t = X v      the weighted Gram pass (smm_dw_tiles_impl<.., GR>);
+//   vxC(v)   = 0.5 K(v),  K(v) = X' diag(w o t) X,  t = X v      the weighted Gram pass (smm_pass<.., GR>);
 //   vxC(v) v = 0.5 X' (w o t^2)                                   RMHMC's T2 term;
 //   G + c vxC(v) = fma(0.5 c, K, G) entry by entry: symmetric, factored by smm_chol, logdet = 2 sum log diag.
 //
@@ -38,33 +38,6 @@
 
 namespace mcmc {
 
-// any of the lane's four values not finite, over the chain's four lanes
-__device__ __forceinline__ bool lmc_not_finite(const double (&u)[4]) {
-    int nf = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) nf |= !(u[e] - u[e] == 0.0);
-    nf |= __shfl_xor(nf, 16, 64);
-    nf |= __shfl_xor(nf, 32, 64);
-    return nf != 0;
-}
-
-// the second pass with the weight's derivative at x: QF the trace term from invG in W; GR the raw weighted Gram
-// matrices K(v) of the tile's chains -> W (lower triangles); T2 X' (w o t^2)
-template <bool QF, bool T2, bool GR>
-__device__ __forceinline__ void lmc_pass(const GlmArgs& a, const GlmPos& p, const SmLds& S, const double (&x)[4],
-                                         const double (&v)[4], double (&u)[4], double (&u2)[4]) {
-    f64x4 U, U2;
-    f64x4 T[16];
-    if (a.m.kind == MK_LOGISTIC) smm_dw_tiles_impl<true, QF, T2, GR>(a, p, S, x, v, U, U2, T);
-    else smm_dw_tiles_impl<false, QF, T2, GR>(a, p, S, x, v, U, U2, T);
-    if (GR) smm_put_tiles(p, S, a.s.d, T);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        u[e] = U[e];
-        u2[e] = U2[e];
-    }
-}
-
 // W = G + (2 cq) vxC from the raw Gram matrix in W and G in the workspace: fma(cq, K, G) entry by entry, then its
 // Cholesky factor in place; returns sum log diag, or NaN on a failed pivot
 __device__ __forceinline__ double lmc_factor(double* Wc, const double* Gc, size_t ld, int d, int nr, int q, double cq) {
@@ -80,11 +53,10 @@ struct LmcGeom {
     bool bad;           // out of support or a failed pivot
 };
 
-// The geometry at x.  Leaves G in st.sm_pG, invG in st.sm_pinvG and in W.  vel (uniform over the workgroup): also the
-// step's velocity chol(invG)' randn (ERMLMC.jl:103), a failed pivot of that factor in bad.
+// The geometry at x (ERMLMC.jl:73-79).  Leaves G in st.sm_pG, invG in st.sm_pinvG and in W.  Every wave of the
+// workgroup calls it (two passes over X).
 __device__ __forceinline__ void lmc_geom(const GlmArgs& a, const GlmPos& p, const SmLds& S, const double (&x)[4],
-                                         double* Gc, double* iGc, bool vel, const Stream& rs, uint32_t chain,
-                                         uint32_t step, LmcGeom& o, double (&v)[4]) {
+                                         double* Gc, double* iGc, LmcGeom& o) {
     const int d = a.s.d, nr = d * (d + 1) / 2;
     const size_t ld = (size_t)a.s.ld;
     double* const Wc = S.W + p.cl;
@@ -94,33 +66,73 @@ __device__ __forceinline__ void lmc_geom(const GlmArgs& a, const GlmPos& p, cons
     o.g = g1[0];
     smm_store_w(Wc, Gc, ld, nr, p.q, p.live);
     smm_wave_sync();
-    o.ld = smm_chol(Wc, d, p.q);
+    o.ld = smm_factor_invert(Wc, S.Y + p.lane, d, nr, p.q, iGc, ld, p.live);
     o.bad = oos || !(o.ld == o.ld);
-    smm_inverse(Wc, S.Y + p.lane, d, p.q, iGc, ld, p.live);
-    smm_mem_sync();
-    smm_load_w(Wc, iGc, ld, nr, p.q, 1.0);
     smm_wave_sync();
-    if (vel) {
-        const double ldi = smm_chol(Wc, d, p.q);
-        o.bad = o.bad || !(ldi == ldi);
-        double z[4];
-        glm_normals<1>(p, rs, chain, step, d, z);
-        smm_put_vec(S.Y, p, z);
-        smm_wave_sync();
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const int r = 4 * p.q + e;
-            double u = 0.0;
-            if (r < d)
-                for (int c = 0; c <= r; ++c) u = __builtin_fma(Wc[16 * smm_tri(r, c)], S.Y[16 * c + p.cl], u);
-            v[e] = u;
-        }
-        smm_wave_sync();
-        smm_load_w(Wc, iGc, ld, nr, p.q, 1.0);
-        smm_wave_sync();
-    }
     double u2[4];
-    lmc_pass<true, false, false>(a, p, S, x, x, o.tr, u2);
+    smm_pass<true, false, false>(a, p, S, x, x, o.tr, u2);
+}
+
+// The step's velocity chol(invG)' randn (ERMLMC.jl:103) from invG in W, which it leaves factored; returns whether a
+// pivot of that factor failed
+__device__ __forceinline__ bool lmc_velocity(const GlmPos& p, const SmLds& S, int d, const Stream& rs, uint32_t chain,
+                                             uint32_t step, double (&v)[4]) {
+    double* const Wc = S.W + p.cl;
+    const double ldi = smm_chol(Wc, d, p.q);
+    double z[4];
+    glm_normals<1>(p, rs, chain, step, d, z);
+    smm_put_vec(S.Y, p, z);
+    smm_wave_sync();
+    smm_lower_mul(Wc, S.Y + p.cl, d, p.q, v);
+    smm_wave_sync();
+    return !(ldi == ldi);
+}
+
+// the trajectory's registers of one chain
+struct LmcTraj {
+    double x[4], v[4], dphi[4];   // position, velocity, dphi = (-grad) + 0.5 traceInvGxdG at the position
+    f64x4 g;                      // gradient at the position
+    double lp, ld;                // log-target and sum log diag cholG at the position
+    double delta;                 // the log-determinants' sum
+    bool dead;                    // the trajectory has failed
+};
+
+// pars + eps v (ERMLMC.jl:129, RMLMC.jl:134), then the geometry there (ERMLMC.jl:131-138, RMLMC.jl:136-142), each
+// taken under the mask.  Every wave of the workgroup calls it (lmc_geom's passes).
+__device__ __forceinline__ void lmc_move(const GlmArgs& a, const GlmPos& p, const SmLds& S, double* Gc, double* iGc,
+                                         double eps, bool on, LmcTraj& T) {
+    double cand[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) cand[e] = T.x[e] + eps * T.v[e];
+    if (rm_take(on, T.dead, smm_not_finite(cand))) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) T.x[e] = cand[e];
+    }
+    LmcGeom o;
+    lmc_geom(a, p, S, T.x, Gc, iGc, o);
+    if (rm_take(on, T.dead, o.bad)) {
+        T.lp = o.lp;
+        T.ld = o.ld;
+        T.g = o.g;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) T.dphi[e] = (-T.g[e]) + 0.5 * o.tr[e];
+    }
+}
+
+// RMLMC's velocity update v - hc (invG (0.5 u2 + dphi)) (RMLMC.jl:124-126, 151), invG in W, u2 = X' (w o t^2): taken
+// into out under the mask
+__device__ __forceinline__ void lmc_kick(const GlmPos& p, const double* Wc, double* V, int d, double hc,
+                                         const double (&u2)[4], bool on, LmcTraj& T, double (&out)[4]) {
+    double sv[4], is[4], cand[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) sv[e] = 0.5 * u2[e] + T.dphi[e];
+    rm_symv(p, Wc, V, d, sv, is);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) cand[e] = T.v[e] - hc * is[e];
+    if (rm_take(on, T.dead, smm_not_finite(cand))) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) out[e] = cand[e];
+    }
 }
 
 template <bool SEMI>
@@ -139,50 +151,43 @@ __global__ __launch_bounds__(256) void lmc_step(GlmArgs a) {
     const size_t ld = (size_t)s.ld;
     const int nn = sa.n_newton;
     const bool tuned = sa.tuner != 0;
-    const int64_t max_leaps = sa.max_leaps;
     double* const Wc = S.W + p.cl;
     double* const V0 = S.Y;
     double* const pGc = a.st.sm_pG + cc;
     double* const piGc = a.st.sm_pinvG + cc;
     double lp = a.st.lp[cc];
-    double eps = tuned ? a.st.t_step[cc] : sa.leap_step;
-    int64_t nl_fixed = tuned ? (int64_t)a.st.t_leaps[cc] : sa.n_leaps;
-    int32_t n_acc = tuned ? a.st.t_acc[cc] : 0;
-    int32_t n_prop = tuned ? a.st.t_prop[cc] : 0;
+    RmTuner tn = rm_tuner_load(a, cc);
     int64_t n_evals = 0;
     for (int t = 0; t < s.nsteps; ++t) {
         const int64_t i = s.step_begin + t;
-        if (tuned) n_prop += 1;
+        if (tuned) tn.n_prop += 1;
+        const double eps = tn.eps;
         const double hc = 0.5 * eps;                                    // (0.5*leapStep)
-        double xp[4], v[4], dphi[4], w4[4], u2[4];
-        f64x4 gp;
-        double ldp, lpp = lp;
-        bool dead;
-        glm_load<1>(a, p, a.st.x, xp);
+        double w4[4], u2[4];
+        LmcTraj T;
+        T.lp = lp;
+        T.delta = 0.0;
+        glm_load<1>(a, p, a.st.x, T.x);
         {
             LmcGeom o;
-            lmc_geom(a, p, S, xp, pGc, piGc, true, rs, chain, (uint32_t)i, o, v);   // ERMLMC.jl:73-79, 103
-            dead = o.bad;
-            ldp = o.ld;
+            lmc_geom(a, p, S, T.x, pGc, piGc, o);                       // ERMLMC.jl:73-79
+            const bool badv = lmc_velocity(p, S, d, rs, chain, (uint32_t)i, T.v);   // ERMLMC.jl:103
+            T.dead = o.bad || badv;
+            T.ld = o.ld;
             f64x4 gs[1];
             glm_load4<1>(a, p, a.st.g, gs);                             // the state's gradient, bit for bit
-            gp = gs[0];
+            T.g = gs[0];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) dphi[e] = (-gp[e]) + 0.5 * o.tr[e];
+            for (int e = 0; e < 4; ++e) T.dphi[e] = (-T.g[e]) + 0.5 * o.tr[e];
         }
         smm_load_w(Wc, pGc, ld, nr, p.q, 1.0);
         smm_wave_sync();
-        rm_symv(p, Wc, V0, d, v, w4);
-        const double quad0 = glm_sum(a, p, none, rm_dot_part(p, d, v, w4));
-        const double E = SEMI ? ((-lp) + ldp) + 0.5 * quad0 : ((-lp) - ldp) + 0.5 * quad0;   // RMLMC.jl:110, ERMLMC.jl:105
-        int nrl;
-        {
-            const u32x4 w = rs.block(chain, (uint32_t)i, 0u, TAG_LMC);
-            nrl = (int)__builtin_ceil(uniform52(w.x, w.y) * (double)nl_fixed);   // ERMLMC.jl:112
-        }
+        rm_symv(p, Wc, V0, d, T.v, w4);
+        const double quad0 = glm_sum(a, p, none, rm_dot_part(p, d, T.v, w4));
+        const double E = SEMI ? ((-lp) + T.ld) + 0.5 * quad0 : ((-lp) - T.ld) + 0.5 * quad0;   // RMLMC.jl:110, ERMLMC.jl:105
+        int nl_wg;                                                      // the workgroup's longest trajectory
+        const int nrl = rm_leaps(iscr, rs.block(chain, (uint32_t)i, 0u, TAG_LMC), tn.nl_fixed, p.live, nl_wg);   // ERMLMC.jl:112
         n_evals += nrl;
-        const int nl_wg = rm_max(iscr, nrl, p.live);                    // the workgroup's longest trajectory
-        double delta = 0.0;
         for (int l = 0; l < nl_wg; ++l) {
             const bool on = l < nrl;                                    // chains that finished keep still
             if (!SEMI) {
@@ -191,12 +196,12 @@ __global__ __launch_bounds__(256) void lmc_step(GlmArgs a) {
                     double rhs[4];
                     smm_load_w(Wc, pGc, ld, nr, p.q, 1.0);
                     smm_wave_sync();
-                    rm_symv(p, Wc, V0, d, v, w4);
+                    rm_symv(p, Wc, V0, d, T.v, w4);
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) rhs[e] = w4[e] - hc * dphi[e];
+                    for (int e = 0; e < 4; ++e) rhs[e] = w4[e] - hc * T.dphi[e];
 #pragma unroll 1
                     for (int sg = 0; sg < 2; ++sg) {
-                        lmc_pass<false, false, true>(a, p, S, xp, v, w4, u2);
+                        smm_pass<false, false, true>(a, p, S, T.x, T.v, w4, u2);
                         const double ldA = lmc_factor(Wc, pGc, ld, d, nr, p.q, sg == 0 ? hc * 0.5 : -(hc * 0.5));
                         if (sg == 0) {
 #pragma unroll
@@ -205,182 +210,66 @@ __global__ __launch_bounds__(256) void lmc_step(GlmArgs a) {
                             double v1[4];
                             smm_solve(Wc, S.vb + p.cl, S.Y + p.lane, d, p.q, v1);
                             smm_wave_sync();
-                            const bool bad = !(ldA == ldA) || lmc_not_finite(v1);
-                            if (on && !dead) {
-                                if (bad) {
-                                    dead = true;
-                                } else {
-                                    delta = delta - 2.0 * ldA;
+                            if (rm_take(on, T.dead, !(ldA == ldA) || smm_not_finite(v1))) {
+                                T.delta = T.delta - 2.0 * ldA;
 #pragma unroll
-                                    for (int e = 0; e < 4; ++e) v[e] = v1[e];
-                                }
+                                for (int e = 0; e < 4; ++e) T.v[e] = v1[e];
                             }
-                        } else if (on && !dead) {
-                            if (!(ldA == ldA)) dead = true;
-                            else delta = delta + 2.0 * ldA;
+                        } else if (rm_take(on, T.dead, !(ldA == ldA))) {
+                            T.delta = T.delta + 2.0 * ldA;
                         }
                     }
-                    if (hs == 0) {
-                        double cand[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) cand[e] = xp[e] + eps * v[e];   // ERMLMC.jl:129
-                        const bool nfx = lmc_not_finite(cand);
-                        if (on && !dead) {
-                            if (nfx) {
-                                dead = true;
-                            } else {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) xp[e] = cand[e];
-                            }
-                        }
-                        LmcGeom o;
-                        lmc_geom(a, p, S, xp, pGc, piGc, false, rs, chain, (uint32_t)i, o, w4);   // ERMLMC.jl:131-138
-                        if (on && !dead) {
-                            if (o.bad) {
-                                dead = true;
-                            } else {
-                                lpp = o.lp;
-                                ldp = o.ld;
-                                gp = o.g;
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) dphi[e] = (-gp[e]) + 0.5 * o.tr[e];
-                            }
-                        }
-                    }
+                    if (hs == 0) lmc_move(a, p, S, pGc, piGc, eps, on, T);
                 }
             } else {
-                double lv[4], lvin[4], is[4];
+                double lv[4], lvin[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) lv[e] = lvin[e] = v[e];
+                for (int e = 0; e < 4; ++e) lv[e] = lvin[e] = T.v[e];
                 smm_load_w(Wc, piGc, ld, nr, p.q, 1.0);
                 smm_wave_sync();
                 for (int k = 0; k < nn; ++k) {                          // RMLMC.jl:122-127
 #pragma unroll
                     for (int e = 0; e < 4; ++e) lvin[e] = lv[e];
-                    lmc_pass<false, true, false>(a, p, S, xp, lv, w4, u2);
-                    double sv[4], cand[4];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) sv[e] = 0.5 * u2[e] + dphi[e];
-                    rm_symv(p, Wc, V0, d, sv, is);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) cand[e] = v[e] - hc * is[e];
-                    const bool nfv = lmc_not_finite(cand);
-                    if (on && !dead) {
-                        if (nfv) {
-                            dead = true;
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) lv[e] = cand[e];
-                        }
-                    }
+                    smm_pass<false, true, false>(a, p, S, T.x, lv, w4, u2);
+                    lmc_kick(p, Wc, V0, d, hc, u2, on, T, lv);
                 }
-                if (on && !dead) {
+                if (on && !T.dead) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = lv[e];           // RMLMC.jl:128
+                    for (int e = 0; e < 4; ++e) T.v[e] = lv[e];         // RMLMC.jl:128
                 }
 #pragma unroll 1
                 for (int sg = 0; sg < 2; ++sg) {
                     // sg 0: vxC of the last pass's input iterate (RMLMC.jl:131); sg 1: of the velocity (RMLMC.jl:146-149)
                     double gv[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) gv[e] = sg == 0 ? lvin[e] : v[e];
-                    lmc_pass<false, true, true>(a, p, S, xp, gv, w4, u2);
+                    for (int e = 0; e < 4; ++e) gv[e] = sg == 0 ? lvin[e] : T.v[e];
+                    smm_pass<false, true, true>(a, p, S, T.x, gv, w4, u2);
                     const double ldA = lmc_factor(Wc, pGc, ld, d, nr, p.q, sg == 0 ? eps * 0.5 : -(eps * 0.5));
-                    if (on && !dead) {
-                        if (!(ldA == ldA)) dead = true;
-                        else delta = sg == 0 ? delta - 2.0 * ldA : delta + 2.0 * ldA;
-                    }
-                    if (sg == 0) {
-                        double cand[4];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) cand[e] = xp[e] + eps * v[e];   // RMLMC.jl:134
-                        const bool nfx = lmc_not_finite(cand);
-                        if (on && !dead) {
-                            if (nfx) {
-                                dead = true;
-                            } else {
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) xp[e] = cand[e];
-                            }
-                        }
-                        LmcGeom o;
-                        lmc_geom(a, p, S, xp, pGc, piGc, false, rs, chain, (uint32_t)i, o, w4);   // RMLMC.jl:136-142
-                        if (on && !dead) {
-                            if (o.bad) {
-                                dead = true;
-                            } else {
-                                lpp = o.lp;
-                                ldp = o.ld;
-                                gp = o.g;
-#pragma unroll
-                                for (int e = 0; e < 4; ++e) dphi[e] = (-gp[e]) + 0.5 * o.tr[e];
-                            }
-                        }
-                    }
+                    if (rm_take(on, T.dead, !(ldA == ldA))) T.delta = sg == 0 ? T.delta - 2.0 * ldA : T.delta + 2.0 * ldA;
+                    if (sg == 0) lmc_move(a, p, S, pGc, piGc, eps, on, T);
                 }
                 smm_load_w(Wc, piGc, ld, nr, p.q, 1.0);
                 smm_wave_sync();
-                double sv[4], cand[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sv[e] = 0.5 * u2[e] + dphi[e];
-                rm_symv(p, Wc, V0, d, sv, is);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) cand[e] = v[e] - hc * is[e];   // RMLMC.jl:151
-                const bool nfv = lmc_not_finite(cand);
-                if (on && !dead) {
-                    if (nfv) {
-                        dead = true;
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] = cand[e];
-                    }
-                }
+                lmc_kick(p, Wc, V0, d, hc, u2, on, T, T.v);             // RMLMC.jl:151
             }
         }
         smm_load_w(Wc, pGc, ld, nr, p.q, 1.0);
         smm_wave_sync();
-        rm_symv(p, Wc, V0, d, v, w4);
-        const double quadp = glm_sum(a, p, none, rm_dot_part(p, d, v, w4));
-        const double Ep = SEMI ? ((-lpp) + ldp) + 0.5 * quadp : ((-lpp) - ldp) + 0.5 * quadp;   // RMLMC.jl:155, ERMLMC.jl:155
-        const double ratio = (E - Ep) + delta;                          // ERMLMC.jl:158
-        const bool acc = !dead && nrl > 0 && (ratio - ratio == 0.0) && glm_mh_short_circuit(rs, chain, (uint32_t)i, ratio);
-        f64x4 go[1] = {gp};
+        rm_symv(p, Wc, V0, d, T.v, w4);
+        const double quadp = glm_sum(a, p, none, rm_dot_part(p, d, T.v, w4));
+        const double Ep = SEMI ? ((-T.lp) + T.ld) + 0.5 * quadp : ((-T.lp) - T.ld) + 0.5 * quadp;   // RMLMC.jl:155, ERMLMC.jl:155
+        const double ratio = (E - Ep) + T.delta;                        // ERMLMC.jl:158
+        const bool acc = !T.dead && nrl > 0 && (ratio - ratio == 0.0) && glm_mh_short_circuit(rs, chain, (uint32_t)i, ratio);
         if (acc) {
-            glm_store<1>(a, p, a.st.x, s.ld, xp);
-            glm_store4<1>(a, p, a.st.g, s.ld, go);
-            lp = lpp;
-            if (tuned) n_acc += 1;
+            lp = T.lp;
+            if (tuned) tn.n_acc += 1;
         }
-        int64_t kk;
-        if (kept_index(i - s.run_step0, s.burnin, s.thinning, s.len, &kk)) {
-            if (!acc) {
-                glm_load<1>(a, p, a.st.x, xp);
-                glm_load4<1>(a, p, a.st.g, go);
-            }
-            glm_store_kept<1>(a, p, kk, s.samples, xp);
-            glm_store_kept4<1>(a, p, kk, s.grads, go);
-            glm_store_bit(a, p, kk, acc);
-        }
-        if (tuned && i <= s.tuner_burnin && (i % sa.adapt_step) == 0) {   // ERMLMC.jl:170-176 (EmpiricalHMCTune)
-            eps = eps * glm_tune_factor(n_acc, n_prop, sa.target_rate);
-            double nlf = __builtin_ceil(sa.target_path / eps);
-            if (nlf > (double)sa.max_step) nlf = (double)sa.max_step;
-            if (nlf > (double)max_leaps) nlf = (double)max_leaps;
-            nl_fixed = (int64_t)nlf;
-            n_acc = 0;
-            n_prop = 0;
-        }
+        f64x4 go[1] = {T.g};
+        smm_commit(a, p, i, acc, T.x, go);
+        rm_tuner_adapt(a, i, tn);                                       // ERMLMC.jl:170-176 (EmpiricalHMCTune)
         smm_mem_sync();                                                // the state the next step's lanes read
     }
-    if (p.live && p.q == 0) {
-        a.st.lp[p.c] = lp;
-        if (tuned) {
-            a.st.t_step[p.c] = eps;
-            a.st.t_leaps[p.c] = (int32_t)nl_fixed;
-            a.st.t_acc[p.c] = n_acc;
-            a.st.t_prop[p.c] = n_prop;
-        }
-    }
+    rm_write_back(a, p, lp, tn);
     glm_count_evals(a, p, n_evals);
 }
 
@@ -392,13 +281,6 @@ hipError_t mcmc_launch_lmc_step(const mcmc::KernelArgs& k, hipStream_t st) {
     if (k.s.d > kSmMaxD || (k.sa.kind != SK_ERMLMC && !semi) || (semi && k.sa.n_newton < 1) ||
         k.st.sm_pG == nullptr || k.st.sm_pinvG == nullptr || (k.m.kind != MK_LOGISTIC && k.m.kind != MK_PROBIT))
         return hipErrorInvalidValue;
-    const GlmShape gs = mcmc_glm_shape(k.s.d, k.m.n);
-    const GlmArgs a = glm_args(k, gs);
-    const void* f = semi ? (const void*)lmc_step<true> : (const void*)lmc_step<false>;
-    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kRmLdsDoubles * sizeof(double)));
-    if (e != hipSuccess) return e;
-    mcmc_note_step_kernel(semi ? "lmc_step<rmlmc>" : "lmc_step<ermlmc>");
-    if (semi) lmc_step<true><<<dim3(glm_grid(k.s.C, gs)), 256, kRmLdsDoubles * sizeof(double), st>>>(a);
-    else lmc_step<false><<<dim3(glm_grid(k.s.C, gs)), 256, kRmLdsDoubles * sizeof(double), st>>>(a);
-    return hipGetLastError();
+    return semi ? smm_launch(lmc_step<true>, "lmc_step<rmlmc>", kRmLdsDoubles, k, st)
+                : smm_launch(lmc_step<false>, "lmc_step<ermlmc>", kRmLdsDoubles, k, st);
 }

@@ -7,7 +7,8 @@
 // The two tensor-derivative terms never form the slabs of dG (dG_r = X' diag(w o X[:, r]) X, the prior adds nothing):
 //   trace(invG dG_r)                 = (X' (w o qf))[r],  qf_o = x_o' invG x_o       (PMALA's U, bit for bit);
 //   0.5 p' invG dG_r invG p          = 0.5 (X' (w o t^2))[r],  t = X v,  v = invG p;
-// both come from smm_dw_tiles, one pass over the staged X tiles producing either or both from the same eta and w.
+// both come from smm_pass (smm_dw_tiles), one pass over the staged X tiles producing either or both from the same eta
+// and w.  The step's frame -- tuner registers, leapfrog count, mask, commit -- is smm_device.hpp's, lmc.hip's too.
 //
 // One step (i the sampler's counter, c the chain):
 //   G = evalt(pars), cholG, invG      smm_evalallt at the state's position (lp and grad come out the state's, bit for
@@ -44,19 +45,6 @@ namespace mcmc {
 constexpr double kRmLog2 = 0x1.62e42fefa39efp-1;
 constexpr double kRmLogPi = 0x1.250d048e7a1bdp+0;
 
-template <bool QF, bool T2>
-__device__ __forceinline__ void rm_pass(const GlmArgs& a, const GlmPos& p, const SmLds& S, const double (&x)[4],
-                                        const double (&v)[4], double (&u)[4], double (&u2)[4]) {
-    f64x4 U, U2;
-    if (a.m.kind == MK_LOGISTIC) smm_dw_tiles<true, QF, T2>(a, p, S, x, v, U, U2);
-    else smm_dw_tiles<false, QF, T2>(a, p, S, x, v, U, U2);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        u[e] = U[e];
-        u2[e] = U2[e];
-    }
-}
-
 __device__ __forceinline__ double rm_hamiltonian(double lp, double ld, double quad, int d) {
     return ((-lp) + 0.5 * ((kRmLog2 + (double)d * kRmLogPi) + 2.0 * ld)) + quad / 2.0;
 }
@@ -78,19 +66,15 @@ __global__ __launch_bounds__(256) void rm_step(GlmArgs a) {
     const size_t ld = (size_t)s.ld;
     const int nn = sa.n_newton;
     const bool tuned = sa.tuner != 0;
-    const int64_t max_leaps = sa.max_leaps;
     double* const Wc = S.W + p.cl;
     double* const V0 = S.Y;
     double* const piGc = a.st.sm_pinvG + cc;
     double lp = a.st.lp[cc];
-    double eps = tuned ? a.st.t_step[cc] : sa.leap_step;
-    int64_t nl_fixed = tuned ? (int64_t)a.st.t_leaps[cc] : sa.n_leaps;
-    int32_t n_acc = tuned ? a.st.t_acc[cc] : 0;
-    int32_t n_prop = tuned ? a.st.t_prop[cc] : 0;
+    RmTuner tn = rm_tuner_load(a, cc);
     int64_t n_evals = 0;
     for (int t = 0; t < s.nsteps; ++t) {
         const int64_t i = s.step_begin + t;
-        if (tuned) n_prop += 1;
+        if (tuned) tn.n_prop += 1;
         double xp[4], mom[4], tr[4], v[4], u2[4];
         f64x4 gp;
         double ld0;
@@ -106,18 +90,9 @@ __global__ __launch_bounds__(256) void rm_step(GlmArgs a) {
             glm_normals<1>(p, rs, chain, (uint32_t)i, d, z);
             smm_put_vec(V0, p, z);
             smm_wave_sync();
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int r = 4 * p.q + e;
-                double u = 0.0;                                         // (cholG' z)[r]: fma chain over c <= r
-                if (r < d)
-                    for (int c = 0; c <= r; ++c) u = __builtin_fma(Wc[16 * smm_tri(r, c)], V0[16 * c + p.cl], u);
-                mom[e] = u;                                             // RMHMC.jl:105
-            }
+            smm_lower_mul(Wc, V0 + p.cl, d, p.q, mom);                  // cholG' z          RMHMC.jl:105
             smm_wave_sync();
-            smm_inverse(Wc, S.Y + p.lane, d, p.q, piGc, ld, p.live);   // invG              RMHMC.jl:101
-            smm_mem_sync();
-            smm_load_w(Wc, piGc, ld, nr, p.q, 1.0);
+            smm_invert(Wc, S.Y + p.lane, d, nr, p.q, piGc, ld, p.live);   // invG            RMHMC.jl:101
             smm_wave_sync();
             f64x4 gs[1];
             glm_load4<1>(a, p, a.st.g, gs);
@@ -125,21 +100,19 @@ __global__ __launch_bounds__(256) void rm_step(GlmArgs a) {
         }
         rm_symv(p, Wc, V0, d, mom, v);
         const double H = rm_hamiltonian(lp, ld0, glm_sum(a, p, none, rm_dot_part(p, d, mom, v)), d);   // RMHMC.jl:107
-        rm_pass<true, false>(a, p, S, xp, xp, tr, u2);                  // trace(invG dG_r)   RMHMC.jl:110-114
-        int nrl;
+        smm_pass<true, false, false>(a, p, S, xp, xp, tr, u2);          // trace(invG dG_r)   RMHMC.jl:110-114
+        const u32x4 w = rs.block(chain, (uint32_t)i, 0u, TAG_RMHMC);
         double eh;
         {
-            const u32x4 w = rs.block(chain, (uint32_t)i, 0u, TAG_RMHMC);
-            const double u = uniform52(w.x, w.y);
             double sn, cs;
             det_sincos2pi_u32(w.w, sn, cs);
             const double nz = bm_radius_u32(w.z, rad_tab_global()) * cs;
             const double ts = nz > 0.5 ? 1.0 : -1.0;                    // RMHMC.jl:117
-            nrl = (int)__builtin_ceil(u * (double)nl_fixed);            // RMHMC.jl:118
-            eh = ts * (eps / 2.0);
+            eh = ts * (tn.eps / 2.0);
         }
+        int nl_wg;                                                      // the workgroup's longest trajectory
+        const int nrl = rm_leaps(iscr, w, tn.nl_fixed, p.live, nl_wg);  // RMHMC.jl:118
         n_evals += nrl;
-        const int nl_wg = rm_max(iscr, nrl, p.live);                    // the workgroup's longest trajectory
         double lpp = lp, ldp = ld0;
         for (int l = 0; l < nl_wg; ++l) {
             const bool on = l < nrl;                                    // chains that finished keep still
@@ -149,7 +122,7 @@ __global__ __launch_bounds__(256) void rm_step(GlmArgs a) {
             for (int k = 0; k < nn; ++k) {                              // RMHMC.jl:123-129
                 rm_symv(p, Wc, V0, d, lm, v);
                 double un[4];
-                rm_pass<false, true>(a, p, S, xp, v, un, u2);
+                smm_pass<false, true, false>(a, p, S, xp, v, un, u2);
                 if (on && !dead) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) lm[e] = mom[e] + eh * ((gp[e] - 0.5 * tr[e]) + 0.5 * u2[e]);
@@ -175,22 +148,12 @@ __global__ __launch_bounds__(256) void rm_step(GlmArgs a) {
                 smm_solve(Wc, S.vb + p.cl, S.Y + p.lane, d, p.q, v1);   // G \ momentum
                 smm_wave_sync();
                 double cand[4];
-                int nf = 0;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    cand[e] = xp[e] + eh * (v1[e] + v2[e]);
-                    nf |= !(cand[e] - cand[e] == 0.0);
-                }
-                nf |= __shfl_xor(nf, 16, 64);
-                nf |= __shfl_xor(nf, 32, 64);
-                const bool badk = oosk || !(ldk == ldk) || nf != 0;
-                if (on && !dead) {
-                    if (badk) {
-                        dead = true;
-                    } else {
+                for (int e = 0; e < 4; ++e) cand[e] = xp[e] + eh * (v1[e] + v2[e]);
+                const bool badk = oosk || !(ldk == ldk) || smm_not_finite(cand);
+                if (rm_take(on, dead, badk)) {
 #pragma unroll
-                        for (int e = 0; e < 4; ++e) lx[e] = cand[e];
-                    }
+                    for (int e = 0; e < 4; ++e) lx[e] = cand[e];
                 }
             }
             if (on && !dead) {
@@ -201,24 +164,17 @@ __global__ __launch_bounds__(256) void rm_step(GlmArgs a) {
                 bool oosc;
                 f64x4 gc[1];
                 const double lpc = smm_evalallt(a, p, S, xp, gc, oosc);   // RMHMC.jl:141, 153, 158
-                const double ldc = smm_chol(Wc, d, p.q);
-                smm_inverse(Wc, S.Y + p.lane, d, p.q, piGc, ld, p.live);   // RMHMC.jl:142
-                smm_mem_sync();
-                smm_load_w(Wc, piGc, ld, nr, p.q, 1.0);
+                const double ldc = smm_factor_invert(Wc, S.Y + p.lane, d, nr, p.q, piGc, ld, p.live);   // RMHMC.jl:142
                 smm_wave_sync();
-                if (on && !dead) {
-                    if (oosc || !(ldc == ldc)) {
-                        dead = true;
-                    } else {
-                        lpp = lpc;
-                        ldp = ldc;
-                        gp = gc[0];
-                    }
+                if (rm_take(on, dead, oosc || !(ldc == ldc))) {
+                    lpp = lpc;
+                    ldp = ldc;
+                    gp = gc[0];
                 }
             }
             rm_symv(p, Wc, V0, d, mom, v);                              // RMHMC.jl:148
             double trn[4];
-            rm_pass<true, true>(a, p, S, xp, v, trn, u2);               // RMHMC.jl:143-151
+            smm_pass<true, true, false>(a, p, S, xp, v, trn, u2);       // RMHMC.jl:143-151
             if (on && !dead) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
@@ -231,43 +187,16 @@ __global__ __launch_bounds__(256) void rm_step(GlmArgs a) {
         const double Hp = rm_hamiltonian(lpp, ldp, glm_sum(a, p, none, rm_dot_part(p, d, mom, v)), d);   // RMHMC.jl:161-162
         const double ratio = H - Hp;                                    // RMHMC.jl:164
         const bool acc = !dead && nrl > 0 && (ratio - ratio == 0.0) && glm_mh_short_circuit(rs, chain, (uint32_t)i, ratio);
-        f64x4 go[1] = {gp};
         if (acc) {
-            glm_store<1>(a, p, a.st.x, s.ld, xp);
-            glm_store4<1>(a, p, a.st.g, s.ld, go);
             lp = lpp;
-            if (tuned) n_acc += 1;
+            if (tuned) tn.n_acc += 1;
         }
-        int64_t kk;
-        if (kept_index(i - s.run_step0, s.burnin, s.thinning, s.len, &kk)) {
-            if (!acc) {
-                glm_load<1>(a, p, a.st.x, xp);
-                glm_load4<1>(a, p, a.st.g, go);
-            }
-            glm_store_kept<1>(a, p, kk, s.samples, xp);
-            glm_store_kept4<1>(a, p, kk, s.grads, go);
-            glm_store_bit(a, p, kk, acc);
-        }
-        if (tuned && i <= s.tuner_burnin && (i % sa.adapt_step) == 0) {   // RMHMC.jl:174-180 (EmpiricalHMCTune)
-            eps = eps * glm_tune_factor(n_acc, n_prop, sa.target_rate);
-            double nlf = __builtin_ceil(sa.target_path / eps);
-            if (nlf > (double)sa.max_step) nlf = (double)sa.max_step;
-            if (nlf > (double)max_leaps) nlf = (double)max_leaps;
-            nl_fixed = (int64_t)nlf;
-            n_acc = 0;
-            n_prop = 0;
-        }
+        f64x4 go[1] = {gp};
+        smm_commit(a, p, i, acc, xp, go);
+        rm_tuner_adapt(a, i, tn);                                       // RMHMC.jl:174-180 (EmpiricalHMCTune)
         smm_mem_sync();                                                // the state the next step's lanes read
     }
-    if (p.live && p.q == 0) {
-        a.st.lp[p.c] = lp;
-        if (tuned) {
-            a.st.t_step[p.c] = eps;
-            a.st.t_leaps[p.c] = (int32_t)nl_fixed;
-            a.st.t_acc[p.c] = n_acc;
-            a.st.t_prop[p.c] = n_prop;
-        }
-    }
+    rm_write_back(a, p, lp, tn);
     glm_count_evals(a, p, n_evals);
 }
 
@@ -278,12 +207,5 @@ hipError_t mcmc_launch_rmhmc_step(const mcmc::KernelArgs& k, hipStream_t st) {
     if (k.s.d > kSmMaxD || k.sa.kind != SK_RMHMC || k.sa.n_newton < 1 || k.st.sm_pinvG == nullptr ||
         (k.m.kind != MK_LOGISTIC && k.m.kind != MK_PROBIT))
         return hipErrorInvalidValue;
-    const GlmShape gs = mcmc_glm_shape(k.s.d, k.m.n);
-    const GlmArgs a = glm_args(k, gs);
-    hipError_t e = hipFuncSetAttribute((const void*)rm_step, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(kRmLdsDoubles * sizeof(double)));
-    if (e != hipSuccess) return e;
-    mcmc_note_step_kernel("rm_step");
-    rm_step<<<dim3(glm_grid(k.s.C, gs)), 256, kRmLdsDoubles * sizeof(double), st>>>(a);
-    return hipGetLastError();
+    return smm_launch(rm_step, "rm_step", kRmLdsDoubles, k, st);
 }

@@ -2,9 +2,12 @@
 // workgroup of four 16-chain tiles, the pass over the observation tiles that forms the log-target, the gradient and the
 // metric tensor on fp64 MFMA (smm_tiles, smm_evalallt), and the small SPD algebra in the chain's four lanes (Cholesky
 // factor, inverse, solve, matvec, quadratic form) with its load / store helpers, and the second pass over the tiles with
-// the weight's derivative (smm_dw_tiles: PMALA's drift correction, RMHMC's two tensor terms).  The arithmetic of every
-// piece is stated in smmala.hip's and pmala.hip's headers and DESIGN.md §4; tests/smmala_oracle.c and its successors
-// restate every sum in the same order.
+// the weight's derivative (smm_dw_tiles, smm_pass: PMALA's drift correction pm_corr, RMHMC's two tensor terms, the
+// Lagrangian samplers' weighted Gram matrix).  On top of them the two frames the step kernels share: the MALA step body
+// (smm_mala_step: smm_step, pm_step) and the trajectory samplers' tuner registers, leapfrog count and mask (RmTuner,
+// rm_leaps, rm_take: rm_step, lmc_step), both closed by smm_commit, and the launch of a kernel of the family
+// (smm_launch).  The arithmetic of every piece is stated in smmala.hip's and pmala.hip's headers and DESIGN.md §4;
+// tests/smmala_oracle.c and its successors restate every sum in the same order.
 #pragma once
 #include "glm_device.hpp"
 
@@ -278,6 +281,33 @@ __device__ __forceinline__ void smm_symv(const double* Wc, const double* Vc, int
         out[e] = t;
     }
 }
+// rows 4q + e of L z, L the lower factor in W, z in the tile's shared vector V (Vc = V + cl): an fma chain over c <= r
+// from zero; zero past d
+__device__ __forceinline__ void smm_lower_mul(const double* Wc, const double* Vc, int d, int q, double (&out)[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int r = 4 * q + e;
+        double t = 0.0;
+        if (r < d)
+            for (int c = 0; c <= r; ++c) t = __builtin_fma(Wc[16 * smm_tri(r, c)], Vc[16 * c], t);
+        out[e] = t;
+    }
+}
+// (L L')^-1 from the factor L in W -> HBM (chain pointer out, stride ld) and from there into W: the lanes that form
+// its columns hand it to the chain's other lanes through HBM.  The caller syncs the wave before it reads W.
+__device__ __forceinline__ void smm_invert(double* Wc, double* Yl, int d, int nr, int q, double* out, size_t ld,
+                                           bool live) {
+    smm_inverse(Wc, Yl, d, q, out, ld, live);
+    smm_mem_sync();
+    smm_load_w(Wc, out, ld, nr, q, 1.0);
+}
+// the chain's SPD matrix in W factored (smm_chol's return) and inverted (smm_invert)
+__device__ __forceinline__ double smm_factor_invert(double* Wc, double* Yl, int d, int nr, int q, double* out,
+                                                    size_t ld, bool live) {
+    const double ldet = smm_chol(Wc, d, q);
+    smm_invert(Wc, Yl, d, nr, q, out, ld, live);
+    return ldet;
+}
 // the lane's partial of e' (M / h) e, M symmetric packed in HBM (chain pointer, stride ld): rows 4q + e in order,
 // t = fma chain over c of (M[r][c] / h) e[c], then fma(e[r], t, partial)
 __device__ __forceinline__ double smm_quad(const double* Mc, size_t ld, const double* Vc, int d, int q, double h,
@@ -345,9 +375,8 @@ __device__ __forceinline__ void pm_stage_first(const GlmArgs& a, const SmLds& S)
 //       (smm_gram_mfma) with the weight RN(w_o t_o) (zero on padded observations): lmc.hip's K(v), 2 vxC(v).  Not
 //       with QF: both use the wave's weight rows.
 template <bool LOGI, bool QF, bool T2, bool GR>
-__device__ __forceinline__ void smm_dw_tiles_impl(const GlmArgs& a, const GlmPos& p, const SmLds& S,
-                                                  const double (&x)[4], const double (&v)[4], f64x4& U, f64x4& U2,
-                                                  f64x4 (&T)[16]) {
+__device__ __forceinline__ void smm_dw_tiles(const GlmArgs& a, const GlmPos& p, const SmLds& S, const double (&x)[4],
+                                             const double (&v)[4], f64x4& U, f64x4& U2, f64x4 (&T)[16]) {
     static_assert(!(QF && GR), "QF and GR share the wave's weight rows");
     const ModelArgs& M = a.m;
     constexpr int SR = glm_row_stride(16);
@@ -448,13 +477,6 @@ __device__ __forceinline__ void smm_dw_tiles_impl(const GlmArgs& a, const GlmPos
     }
 }
 
-template <bool LOGI, bool QF, bool T2>
-__device__ __forceinline__ void smm_dw_tiles(const GlmArgs& a, const GlmPos& p, const SmLds& S, const double (&x)[4],
-                                             const double (&v)[4], f64x4& U, f64x4& U2) {
-    f64x4 T[16];
-    smm_dw_tiles_impl<LOGI, QF, T2, false>(a, p, S, x, v, U, U2, T);
-}
-
 // the tile's sixteen accumulators -> the workspace S.W (lower triangles), as smm_evalallt lays the tensor out
 __device__ __forceinline__ void smm_put_tiles(const GlmPos& p, const SmLds& S, int d, const f64x4 (&T)[16]) {
 #pragma unroll
@@ -466,6 +488,24 @@ __device__ __forceinline__ void smm_put_tiles(const GlmPos& p, const SmLds& S, i
         }
     }
     smm_wave_sync();
+}
+
+// The second pass (smm_dw_tiles) at x for the model's link, at the lane's own coordinates: QF the trace term
+// u = X' (w o qf) from invG in W; T2 u2 = X' (w o t^2), t = X v; GR the raw weighted Gram matrices K(v) of the tile's
+// chains -> W (lower triangles).  Every wave of the workgroup calls it.
+template <bool QF, bool T2, bool GR>
+__device__ __forceinline__ void smm_pass(const GlmArgs& a, const GlmPos& p, const SmLds& S, const double (&x)[4],
+                                         const double (&v)[4], double (&u)[4], double (&u2)[4]) {
+    f64x4 U, U2;
+    f64x4 T[16];
+    if (a.m.kind == MK_LOGISTIC) smm_dw_tiles<true, QF, T2, GR>(a, p, S, x, v, U, U2, T);
+    else smm_dw_tiles<false, QF, T2, GR>(a, p, S, x, v, U, U2, T);
+    if (GR) smm_put_tiles(p, S, a.s.d, T);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        u[e] = U[e];
+        u2[e] = U2[e];
+    }
 }
 
 // (L L') \ b from the factor L in W: b in the tile's shared vector B [16 coords][16 chains] (Bc = B + cl); every lane
@@ -489,6 +529,174 @@ __device__ __forceinline__ void smm_solve(const double* Wc, const double* Bc, do
     for (int e = 0; e < 4; ++e) out[e] = 4 * q + e < d ? Yl[64 * (4 * q + e)] : 0.0;
 }
 
+// out = M in, M the chain's symmetric packed matrix in W, through the tile's shared vector V
+__device__ __forceinline__ void rm_symv(const GlmPos& p, const double* Wc, double* V, int d, const double (&in)[4],
+                                        double (&out)[4]) {
+    smm_put_vec(V, p, in);
+    smm_wave_sync();
+    smm_symv(Wc, V + p.cl, d, p.q, out);
+    smm_wave_sync();
+}
+
+// c = invG (X' (w o qf)) at x, invG in S.W; V: one of the tile's shared vectors.  Every wave of the workgroup calls it.
+__device__ __forceinline__ void pm_corr(const GlmArgs& a, const GlmPos& p, const SmLds& S, const double (&x)[4],
+                                        double* V, double (&cv)[4]) {
+    double u[4], u2[4];
+    smm_pass<true, false, false>(a, p, S, x, x, u, u2);
+    rm_symv(p, S.W + p.cl, V, a.s.d, u, cv);
+}
+
+// any of the lane's four values not finite, over the chain's four lanes
+__device__ __forceinline__ bool smm_not_finite(const double (&u)[4]) {
+    int nf = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) nf |= !(u[e] - u[e] == 0.0);
+    nf |= __shfl_xor(nf, 16, 64);
+    nf |= __shfl_xor(nf, 32, 64);
+    return nf != 0;
+}
+
+// A step's end: the accepted proposal (x, g) becomes the state; step i's kept sample (on reject the state, read back
+// into x and g) and its accept bit
+__device__ __forceinline__ void smm_commit(const GlmArgs& a, const GlmPos& p, int64_t i, bool acc, double (&x)[4],
+                                           f64x4 (&g)[1]) {
+    const StepArgs& s = a.s;
+    if (acc) {
+        glm_store<1>(a, p, a.st.x, s.ld, x);
+        glm_store4<1>(a, p, a.st.g, s.ld, g);
+    }
+    int64_t kk;
+    if (kept_index(i - s.run_step0, s.burnin, s.thinning, s.len, &kk)) {
+        if (!acc) {
+            glm_load<1>(a, p, a.st.x, x);
+            glm_load4<1>(a, p, a.st.g, g);
+        }
+        glm_store_kept<1>(a, p, kk, s.samples, x);
+        glm_store_kept4<1>(a, p, kk, s.grads, g);
+        glm_store_bit(a, p, kk, acc);
+    }
+}
+
+// ------------------------------------------------------------------ the MALA pair (smmala.hip, pmala.hip)
+// SMMALA.jl:72-122 and, with CORR (the drift correction c), PMALA.jl:85-140: one step per loop pass; the state (pars,
+// logTarget, grad, G, invG, firstTerm and PMALA's c) lives in HBM.  smem: the workgroup's dynamic LDS.
+template <bool CORR>
+__device__ __forceinline__ void smm_mala_step(const GlmArgs& a, double* smem) {
+    const StepArgs& s = a.s;
+    const SamplerArgs& sa = a.sa;
+    const GlmPos p = glm_pos(a);
+    const SmLds S = smm_lds(smem, p.wave);
+    const GlmLds none{};
+    const Stream rs{s.key0, s.key1};
+    const uint32_t chain = s.chain0 + (uint32_t)p.c;
+    const int64_t cc = p.live ? p.c : 0;
+    const int d = s.d, nr = d * (d + 1) / 2;
+    const size_t ld = (size_t)s.ld;
+    double* const Wc = S.W + p.cl;
+    double* const V0 = S.Y;
+    double* const V1 = S.Y + 256;
+    double* const Gc = a.st.sm_G + cc;
+    double* const iGc = a.st.sm_invG + cc;
+    double* const pGc = a.st.sm_pG + cc;
+    double* const piGc = a.st.sm_pinvG + cc;
+    double lp = a.st.lp[cc];
+    double h = sa.tuner ? a.st.t_step[cc] : sa.drift_step;
+    int32_t n_acc = sa.tuner ? a.st.t_acc[cc] : 0;
+    int32_t n_prop = sa.tuner ? a.st.t_prop[cc] : 0;
+    for (int t = 0; t < s.nsteps; ++t) {
+        const int64_t i = s.step_begin + t;
+        if (sa.tuner) n_prop += 1;
+        const double half = h / 2.0;
+        double xp[4], ev[4];
+        // U = chol(h invG): its transpose, the lower factor, in W
+        smm_load_w(Wc, iGc, ld, nr, p.q, h);
+        smm_wave_sync();
+        const double ld1 = smm_chol(Wc, d, p.q);
+        bool bad = !(ld1 == ld1);
+        {
+            double z[4], x[4], ft[4], cv[4], u[4];
+            glm_normals<1>(p, rs, chain, (uint32_t)i, d, z);
+            glm_load<1>(a, p, a.st.x, x);
+            glm_load<1>(a, p, a.st.sm_ft, ft);
+            if (CORR) glm_load<1>(a, p, a.st.pm_c, cv);
+            smm_put_vec(V0, p, z);
+            smm_wave_sync();
+            smm_lower_mul(Wc, V0 + p.cl, d, p.q, u);                    // U' z
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const bool in = 4 * p.q + e < d;
+                const double pm = x[e] + half * (CORR ? ft[e] - cv[e] : ft[e]);   // SMMALA.jl:85, PMALA.jl:94
+                xp[e] = in ? pm + u[e] : 0.0;                           // SMMALA.jl:88, PMALA.jl:98
+                ev[e] = in ? pm - xp[e] : 0.0;
+            }
+        }
+        smm_put_vec(V1, p, ev);
+        smm_wave_sync();
+        // probNewGivenOld = -sum(log(diag(U))) - 0.5 e' (G / h) e     SMMALA.jl:93-94, PMALA.jl:103-104
+        const double quad1 = glm_sum(a, p, none, smm_quad(Gc, ld, V1 + p.cl, d, p.q, h, ev));
+        const double qf = (-ld1) - 0.5 * quad1;
+        smm_wave_sync();
+        bool oos;
+        f64x4 gp[1];
+        const double lpp = smm_evalallt(a, p, S, xp, gp, oos);         // SMMALA.jl:90, PMALA.jl:101
+        smm_store_w(Wc, pGc, ld, nr, p.q, p.live);
+        // proposedG = L L', proposedInvG   SMMALA.jl:97, PMALA.jl:106
+        const double ldg = smm_factor_invert(Wc, S.Y + p.lane, d, nr, p.q, piGc, ld, p.live);
+        bad = bad || !(ldg == ldg);
+        double pft[4], pc[4];
+        {
+            const double gv[4] = {gp[0][0], gp[0][1], gp[0][2], gp[0][3]};
+            rm_symv(p, Wc, V0, d, gv, pft);                            // proposedFirstTerm   SMMALA.jl:98, PMALA.jl:107
+        }
+        if (CORR) pm_corr(a, p, S, xp, V0, pc);                        // sum(proposedSecondTerm, 2)   PMALA.jl:108-111
+        for (int idx = p.q; idx < nr; idx += 4) Wc[16 * idx] = h * Wc[16 * idx];
+        smm_wave_sync();
+        const double ld2 = smm_chol(Wc, d, p.q);                       // chol(h proposedInvG)
+        bad = bad || !(ld2 == ld2);
+        {
+            double x[4];
+            glm_load<1>(a, p, a.st.x, x);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)   // SMMALA.jl:99-101, PMALA.jl:114, 117
+                ev[e] = 4 * p.q + e < d ? (xp[e] + half * (CORR ? pft[e] - pc[e] : pft[e])) - x[e] : 0.0;
+        }
+        smm_put_vec(V1, p, ev);
+        smm_wave_sync();
+        const double quad2 = glm_sum(a, p, none, smm_quad(pGc, ld, V1 + p.cl, d, p.q, h, ev));
+        const double qb = (-ld2) - 0.5 * quad2;                        // probOldGivenNew
+        const double ratio = ((lpp + qb) - lp) - qf;                   // SMMALA.jl:104, PMALA.jl:119
+        // a proposal out of support or with a failed pivot is rejected (the reference throws out of chol)
+        const bool acc = !(bad || oos) && glm_mh_short_circuit(rs, chain, (uint32_t)i, ratio);
+        if (acc) {
+            glm_store<1>(a, p, a.st.sm_ft, s.ld, pft);
+            if (CORR) glm_store<1>(a, p, a.st.pm_c, s.ld, pc);
+            if (p.live)
+                for (int idx = p.q; idx < nr; idx += 4) {
+                    Gc[(size_t)idx * ld] = pGc[(size_t)idx * ld];
+                    iGc[(size_t)idx * ld] = piGc[(size_t)idx * ld];
+                }
+            lp = lpp;
+            if (sa.tuner) n_acc += 1;
+        }
+        smm_commit(a, p, i, acc, xp, gp);
+        // SMMALA.jl:113-119, PMALA.jl:131-137 (EmpiricalMALATune)
+        if (sa.tuner && i <= s.tuner_burnin && (i % sa.adapt_step) == 0) {
+            h = h * glm_tune_factor(n_acc, n_prop, sa.target_rate);
+            n_acc = 0;
+            n_prop = 0;
+        }
+        smm_mem_sync();                                                // the state the next step's lanes read
+    }
+    if (p.live && p.q == 0) {
+        a.st.lp[p.c] = lp;
+        if (sa.tuner) {
+            a.st.t_step[p.c] = h;
+            a.st.t_acc[p.c] = n_acc;
+            a.st.t_prop[p.c] = n_prop;
+        }
+    }
+}
+
 // ------------------------------------------------------------------ the trajectory samplers (rmhmc.hip, lmc.hip)
 // smm_device.hpp's carve-up, then the leapfrog count's maximum
 constexpr int kRmLdsDoubles = kSmLdsDoubles + 2;
@@ -505,13 +713,20 @@ __device__ __forceinline__ int rm_max(int* iscr, int v, bool live) {
     return r;
 }
 
-// out = M in, M the chain's symmetric packed matrix in W, through the tile's shared vector V
-__device__ __forceinline__ void rm_symv(const GlmPos& p, const double* Wc, double* V, int d, const double (&in)[4],
-                                        double (&out)[4]) {
-    smm_put_vec(V, p, in);
-    smm_wave_sync();
-    smm_symv(Wc, V + p.cl, d, p.q, out);
-    smm_wave_sync();
+// nRandomLeaps = ceil(uniform52(w0, w1) nLeaps) of the step's block w, and in nl_wg the workgroup's longest trajectory
+// (rm_max: every wave must reach it)
+__device__ __forceinline__ int rm_leaps(int* iscr, const u32x4& w, int64_t nl_fixed, bool live, int& nl_wg) {
+    const int nrl = (int)__builtin_ceil(uniform52(w.x, w.y) * (double)nl_fixed);
+    nl_wg = rm_max(iscr, nrl, live);
+    return nrl;
+}
+
+// A masked update of a trajectory: a chain that has finished (!on) or has failed (dead) keeps still, and a bad value
+// kills the trajectory.  Returns whether the chain takes the update.  Never around a pass over X.
+__device__ __forceinline__ bool rm_take(bool on, bool& dead, bool bad) {
+    if (!on || dead) return false;
+    dead = bad;
+    return !bad;
 }
 
 // the lane's partial of a' b over its coordinates
@@ -523,8 +738,62 @@ __device__ __forceinline__ double rm_dot_part(const GlmPos& p, int d, const doub
     return part;
 }
 
-static hipError_t smm_lds_attr(const void* f) {
-    return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(kSmLdsDoubles * sizeof(double)));
+// The chain's EmpiricalHMCTune registers: leapStep, nLeaps and the window's counts (without a tuner the sampler's
+// constants, and the counts stay 0)
+struct RmTuner {
+    double eps;
+    int64_t nl_fixed;
+    int32_t n_acc, n_prop;
+};
+__device__ __forceinline__ RmTuner rm_tuner_load(const GlmArgs& a, int64_t cc) {
+    const SamplerArgs& sa = a.sa;
+    const bool tuned = sa.tuner != 0;
+    RmTuner T;
+    T.eps = tuned ? a.st.t_step[cc] : sa.leap_step;
+    T.nl_fixed = tuned ? (int64_t)a.st.t_leaps[cc] : sa.n_leaps;
+    T.n_acc = tuned ? a.st.t_acc[cc] : 0;
+    T.n_prop = tuned ? a.st.t_prop[cc] : 0;
+    return T;
+}
+// the window's end at step i: leapStep by the window's rate, nLeaps = ceil(targetPath / leapStep) under its two caps
+__device__ __forceinline__ void rm_tuner_adapt(const GlmArgs& a, int64_t i, RmTuner& T) {
+    const SamplerArgs& sa = a.sa;
+    if (sa.tuner && i <= a.s.tuner_burnin && (i % sa.adapt_step) == 0) {
+        T.eps = T.eps * glm_tune_factor(T.n_acc, T.n_prop, sa.target_rate);
+        double nlf = __builtin_ceil(sa.target_path / T.eps);
+        if (nlf > (double)sa.max_step) nlf = (double)sa.max_step;
+        if (nlf > (double)sa.max_leaps) nlf = (double)sa.max_leaps;
+        T.nl_fixed = (int64_t)nlf;
+        T.n_acc = 0;
+        T.n_prop = 0;
+    }
+}
+// the launch's end: the chain's log-target and tuner registers -> the state (the chain's lane q = 0)
+__device__ __forceinline__ void rm_write_back(const GlmArgs& a, const GlmPos& p, double lp, const RmTuner& T) {
+    if (p.live && p.q == 0) {
+        a.st.lp[p.c] = lp;
+        if (a.sa.tuner) {
+            a.st.t_step[p.c] = T.eps;
+            a.st.t_leaps[p.c] = (int32_t)T.nl_fixed;
+            a.st.t_acc[p.c] = T.n_acc;
+            a.st.t_prop[p.c] = T.n_prop;
+        }
+    }
+}
+
+// One launch of a kernel of the family: glm_grid workgroups of 256 threads with lds_doubles of dynamic LDS.  note: the
+// step kernel's name for mcmc_note_step_kernel, or NULL.  rest: the kernel's arguments after GlmArgs.
+template <typename... P, typename... A>
+static hipError_t smm_launch(void (*kern)(GlmArgs, P...), const char* note, int lds_doubles, const KernelArgs& k,
+                             hipStream_t st, A... rest) {
+    const GlmShape gs = mcmc_glm_shape(k.s.d, k.m.n);
+    const GlmArgs a = glm_args(k, gs);
+    const size_t lds = (size_t)lds_doubles * sizeof(double);
+    const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    if (note) mcmc_note_step_kernel("%s", note);
+    kern<<<dim3(glm_grid(k.s.C, gs)), 256, lds, st>>>(a, rest...);
+    return hipGetLastError();
 }
 
 }  // namespace mcmc
