@@ -421,7 +421,7 @@ def test_glm_continue_and_shard(gpu):
 @pytest.mark.parametrize("sname", ["hmcda", "hmc_tuned"])
 @pytest.mark.parametrize("kind,d", [("linear", 20), ("logistic", 200)])
 def test_glm_trajectory_order_continue(gpu, sname, kind, d):
-    """Regression HMC / HMCDA launch their chains sorted by trajectory length (runtime.cpp glm_trajectory_order):
+    """Regression HMC / HMCDA launch their chains sorted by trajectory length (host/run.cpp glm_trajectory_order):
     after an adapting run the per-chain leapStep (HMCDA) or nLeaps (tuned HMC) differ, so the continued run's tile
     -> chain map is a real permutation; samples, gradients, accept bits, final state, evaluation counts and the
     adapted state stay bitwise the oracle's (which knows nothing of tiles)."""
@@ -460,7 +460,7 @@ def test_glm_trajectory_order_continue(gpu, sname, kind, d):
                                             ("probit", 160, 160, "hmc_tuned")])
 def test_glm_tile_pairing_and_skip(gpu, kind, d, C, sname):
     """d-sliced regression HMCDA with two chain tiles a workgroup (128 < d <= 512) and whole 32-chain workgroups: the
-    runtime gives workgroup w the w-th longest and the w-th shortest sorted tile (runtime.cpp glm_trajectory_order),
+    runtime gives workgroup w the w-th longest and the w-th shortest sorted tile (host/run.cpp glm_trajectory_order),
     and glm_hmc's tiles whose chains have all ended their trajectories skip their evaluations (GLM_TILE_SKIP) while
     the other tile of their workgroup runs on.  Samples, gradients, accept bits, final state, evaluation counts and
     the adapted leapSteps stay bitwise the oracle's."""
@@ -534,7 +534,7 @@ def test_logistic_mala_minus_inf_rule_each_row(gpu, obs):
 def test_covariates_that_can_overflow_to_nan_are_refused(gpu, kind):
     """X vars overflowing with mixed signs gives a NaN eta, which the reference's LLAcc turns into -Inf; the kernels
     clamp |eta| into their tables, so mcmc_model_create refuses data whose row L1 norm times the largest |vars| of
-    finite prior density can reach 2^1022 (runtime.cpp), and accepts the same rows scaled into range."""
+    finite prior density can reach 2^1022 (host/model.cpp), and accepts the same rows scaled into range."""
     from mcmchip import _lib
     X = np.array([[1.0, 1e200], [1.0, -1e200], [1.0, 3.0]])
     Y = np.array([0.0, 1.0, 1.0])
