@@ -19,14 +19,28 @@ int mcmc_set_error(int code, const std::string& msg) {
 
 // the step kernel instance the last launch function on this thread dispatched (kernels_api.hpp)
 static thread_local char g_step_kernel[160];
+static thread_local bool g_noted;                      // false: cleared (g_step_kernel keeps the text it was formatted to)
+static thread_local mcmc::KernelInstance g_inst;       // the instance g_step_kernel was formatted from, while
+static thread_local const char* g_inst_model;          // g_inst_model is not NULL
 void mcmc_note_step_kernel(const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_step_kernel, sizeof g_step_kernel, fmt, ap);
     va_end(ap);
+    g_inst_model = nullptr;
+    g_noted = true;
 }
-const char* mcmc_last_step_kernel() { return g_step_kernel; }
-void mcmc_clear_step_kernel() { g_step_kernel[0] = 0; }
+// a run of one-step launches notes the same instance every time: it is formatted once
+void mcmc_note_step_instance(const mcmc::KernelInstance& k, const char* model) {
+    if (g_inst_model != model || !(g_inst == k)) {
+        mcmc::plan_kernel_name(g_step_kernel, sizeof g_step_kernel, k, model);
+        g_inst = k;
+        g_inst_model = model;
+    }
+    g_noted = true;
+}
+const char* mcmc_last_step_kernel() { return g_noted ? g_step_kernel : ""; }
+void mcmc_clear_step_kernel() { g_noted = false; }
 
 extern "C" int mcmc_abi_version(void) { return MCMC_ABI_VERSION; }
 extern "C" int mcmc_device_count(int* count) {

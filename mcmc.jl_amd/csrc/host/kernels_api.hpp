@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../common.hpp"
+#include "../kernels/launch_plan.hpp"
 
 namespace mcmc {
 struct KernelArgs {
@@ -16,8 +17,10 @@ struct KernelArgs {
 
 // The step kernel a launch function dispatched, as "family<template arguments>" (the instance name rocprofv3
 // shows, without the namespace): the launch functions record it, mcmc_chains_step_kernel reports it (tests and
-// bench.py check which instance ran).  Host-side, thread-local; printf-style.
+// bench.py check which instance ran).  Host-side, thread-local; printf-style, or an instance of the launch plan
+// (kernels/launch_plan.hpp plan_kernel_name formats it) with the model class's kName, a string that outlives the call.
 void mcmc_note_step_kernel(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+void mcmc_note_step_instance(const mcmc::KernelInstance& k, const char* model);
 const char* mcmc_last_step_kernel();
 
 // lane-per-chain kernels (d <= 32), state [d][ld]
@@ -31,7 +34,8 @@ int mcmc_lpc_max_d();
 hipError_t mcmc_launch_nuts(const mcmc::KernelArgs& a, int init, hipStream_t st);
 int mcmc_nuts_max_d();
 int mcmc_nuts_max_doublings();
-// wave-per-chain kernels (32 < d <= 4096), state [C][ld] (ld = row stride, multiple of 4)
+// wave- and block-per-chain kernels (32 < d <= mcmc_wpc_max_d() = 16384; RAM: d <= mcmc_wpc_ram_max_d() = 1024),
+// state [C][ld] (ld = row stride, multiple of 4)
 hipError_t mcmc_launch_wpc_step(const mcmc::KernelArgs& a, hipStream_t st);
 hipError_t mcmc_launch_wpc_eval(const mcmc::KernelArgs& a, const double* xin, double* lp, double* g, int check,
                                 hipStream_t st);

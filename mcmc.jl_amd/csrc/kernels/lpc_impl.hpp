@@ -1,33 +1,30 @@
 // lpc_impl.hpp -- lane-per-chain kernels (d <= 32): one thread = one chain; see samplers.hpp for the
 // step code and its reference lines.  Included by one translation unit per model (lpc_<model>.hip)
-// so that the instantiations compile in parallel; lpc.hip dispatches on the model kind.
+// so that the instantiations compile in parallel; lpc.hip looks the model's unit up.  Which instance a launch
+// runs, and its block size, is launch_plan.hpp's.
 #pragma once
 #include "../samplers.hpp"
 #include "layout_api.hpp"
 
 namespace mcmc {
+static_assert(kBlock == kPlanBlock, "the plan's default block size is the kernels'");
 
 // F: d == 4 NB (LaneChain FULL); US: uniform RWM scale.  RWM (config 2, d = 3): 512-thread blocks reading the
 // Box-Muller tables from LDS (56 KB a block: two blocks a CU, four waves per SIMD), so 2^20 chains are exactly four
 // rounds of the 512 resident blocks (768-thread blocks, six waves per SIMD, left a 2/3-full last round: CU busy
-// 0.87 of the launch, 1.47e11 against 1.63e11 chain-steps/s); MALA / HMC (256 threads, two waves per SIMD by their
-// registers, so two blocks a CU) read them from LDS too
-constexpr int kLpcRwmThreads = 512;
+// 0.87 of the launch, 1.47e11 against 1.63e11 chain-steps/s); MALA / HMC (lpc_grad_threads: two waves per SIMD by
+// their registers at d > 8, so two blocks a CU) read them from LDS too
 template <int NB, bool F, class M, bool US>
 __global__ __launch_bounds__(kLpcRwmThreads) void lpc_rwm(KernelArgs a) {
     rwm_body<LaneChain<NB, F, false, kLpcRwmThreads, kTabLds>, M, US>(a);
 }
-// MALA / HMC block size: two 56 KB-LDS blocks a CU, sized so that they fill the occupancy the registers allow
-// (d <= 4: 125 VGPRs, four waves per SIMD; d <= 8: ~155, three; d <= 16: ~200-240, two)
-template <int NB>
-constexpr int lpc_grad_threads() { return NB == 1 ? 512 : (NB == 2 ? 768 : 256); }
 template <int NB, bool F, class M>
-__global__ __launch_bounds__((lpc_grad_threads<NB>()), (lpc_grad_threads<NB>() / 256)) void lpc_mala(KernelArgs a) {
-    mala_body<LaneChain<NB, F, false, lpc_grad_threads<NB>(), kTabLds>, M>(a);
+__global__ __launch_bounds__((lpc_grad_threads(NB)), (lpc_grad_threads(NB) / 256)) void lpc_mala(KernelArgs a) {
+    mala_body<LaneChain<NB, F, false, lpc_grad_threads(NB), kTabLds>, M>(a);
 }
 template <int NB, bool F, class M, bool DA>
-__global__ __launch_bounds__((lpc_grad_threads<NB>()), (lpc_grad_threads<NB>() / 256)) void lpc_hmc(KernelArgs a) {
-    hmc_body<LaneChain<NB, F, false, lpc_grad_threads<NB>(), kTabLds>, M, DA>(a);
+__global__ __launch_bounds__((lpc_grad_threads(NB)), (lpc_grad_threads(NB) / 256)) void lpc_hmc(KernelArgs a) {
+    hmc_body<LaneChain<NB, F, false, lpc_grad_threads(NB), kTabLds>, M, DA>(a);
 }
 template <int NB, class M>
 __global__ __launch_bounds__(kBlock) void lpc_eval(KernelArgs a, const double* xin, double* lp, double* g,
@@ -41,15 +38,13 @@ __global__ __launch_bounds__(kBlock) void lpc_eval(KernelArgs a, const double* x
 // 768-thread block; 2 with masks); HMC's x0, x, momentum and carried kicks need ~220 (2 waves, where the lane-per-
 // chain d = 32 kernel fitted one).  The Box-Muller tables are read from LDS.  MALA's block sizes, measured (r3g, d = 32,
 // 2^20 chains): 768 threads / LDS tables 0.0957 ms a step, 512 / LDS (two waves) 0.0966, 256 / global tables 0.1031.
-template <int NB, bool F>
-constexpr int lpp_mala_threads() { return F ? 768 : 512; }
 template <int NB, bool F, class M, bool US>
 __global__ __launch_bounds__(512, F && US ? 4 : 3) void lpp_rwm(KernelArgs a) {
     rwm_body<PairChain<NB, F, 512, kTabLds>, M, US>(a);
 }
 template <int NB, bool F, class M>
-__global__ __launch_bounds__((lpp_mala_threads<NB, F>()), F ? 3 : 2) void lpp_mala(KernelArgs a) {
-    mala_body<PairChain<NB, F, lpp_mala_threads<NB, F>(), kTabLds>, M>(a);
+__global__ __launch_bounds__((lpp_mala_threads(F)), F ? 3 : 2) void lpp_mala(KernelArgs a) {
+    mala_body<PairChain<NB, F, lpp_mala_threads(F), kTabLds>, M>(a);
 }
 template <int NB, bool F, class M, bool DA>
 __global__ __launch_bounds__(512, 2) void lpp_hmc(KernelArgs a) { hmc_body<PairChain<NB, F, 512, kTabLds>, M, DA>(a); }
@@ -66,7 +61,6 @@ __global__ __launch_bounds__(kBlock) void lpp_eval(KernelArgs a, const double* x
 // the current half, so the generation is off the dependent path.  Wave 0 prefetches step j+1's increments into
 // registers before it runs step j.  rwm_body's operations on the same values (x + RN(z scale), the
 // short-circuit test against det_log(u)), so the chains are bitwise the same.
-constexpr int kLaMaxChains = 64;
 constexpr int kLaGen = kBlock - 64;                  // generating threads
 template <int NB, class M, bool US>
 __global__ __launch_bounds__(kBlock) void lpc_rwm_la(KernelArgs a) {
@@ -335,139 +329,6 @@ __global__ __launch_bounds__(kBlock) void lpc_rwm_spec(KernelArgs a) {
     }
 }
 
-template <int D, class M>
-static void lpc_spec_launch(const KernelArgs& a, hipStream_t st) {
-    if (a.s.scale_uniform) lpc_rwm_spec<D, M, true><<<1, kBlock, 0, st>>>(a);
-    else lpc_rwm_spec<D, M, false><<<1, kBlock, 0, st>>>(a);
-}
-
-// 16 < d <= 32 (NB = ceil(d/4) > 4): the two-lanes-per-chain kernels, NBL = ceil(NB / 2) blocks per lane
-template <int NBL, bool F, class M>
-static hipError_t lpp_launch(const KernelArgs& a, hipStream_t st) {
-    auto grid = [&](int threads) { return dim3((unsigned)((a.s.C + threads / 2 - 1) / (threads / 2))); };
-    const char* b = F ? "true" : "false";
-    const char* us = a.s.scale_uniform ? "true" : "false";
-    constexpr int TM = lpp_mala_threads<NBL, F>();
-    switch (a.sa.kind) {
-        case SK_RWM:
-            mcmc_note_step_kernel("lpp_rwm<%d, %s, %s, %s>", NBL, b, M::kName, us);
-            if (a.s.scale_uniform) lpp_rwm<NBL, F, M, true><<<grid(512), 512, 0, st>>>(a);
-            else lpp_rwm<NBL, F, M, false><<<grid(512), 512, 0, st>>>(a);
-            break;
-        case SK_MALA:
-            mcmc_note_step_kernel("lpp_mala<%d, %s, %s>", NBL, b, M::kName);
-            lpp_mala<NBL, F, M><<<grid(TM), TM, 0, st>>>(a);
-            break;
-        case SK_HMC:
-            mcmc_note_step_kernel("lpp_hmc<%d, %s, %s, false>", NBL, b, M::kName);
-            lpp_hmc<NBL, F, M, false><<<grid(512), 512, 0, st>>>(a);
-            break;
-        case SK_HMCDA:
-            mcmc_note_step_kernel("lpp_hmc<%d, %s, %s, true>", NBL, b, M::kName);
-            lpp_hmc<NBL, F, M, true><<<grid(512), 512, 0, st>>>(a);
-            break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
-template <int NB, bool F, class M>
-static hipError_t lpc_launch_model(const KernelArgs& a, hipStream_t st) {
-    const char* us = a.s.scale_uniform ? "true" : "false";
-    const bool few = a.sa.kind == SK_RWM && a.s.C <= kLaMaxChains;      // lpc_rwm_la (split order for d > 16)
-    if constexpr (NB > 4) {
-        if (!few) return lpp_launch<(NB + 1) / 2, F && (NB % 2 == 0), M>(a, st);
-        mcmc_note_step_kernel("lpc_rwm_la<%d, %s, %s>", NB, M::kName, us);
-        if (a.s.scale_uniform) lpc_rwm_la<NB, M, true><<<1, kBlock, 0, st>>>(a);
-        else lpc_rwm_la<NB, M, false><<<1, kBlock, 0, st>>>(a);
-    } else {
-        const dim3 grid((unsigned)((a.s.C + kBlock - 1) / kBlock));
-        auto gridT = [&](int threads) { return dim3((unsigned)((a.s.C + threads - 1) / threads)); };
-        const char* b = F ? "true" : "false";
-        switch (a.sa.kind) {
-            case SK_RWM:
-                if (NB == 1 && a.s.C == 1) {
-                    mcmc_note_step_kernel("lpc_rwm_spec<%d, %s, %s>", (int)a.s.d, M::kName, us);
-                    switch (a.s.d) {
-                        case 1: lpc_spec_launch<1, M>(a, st); break;
-                        case 2: lpc_spec_launch<2, M>(a, st); break;
-                        case 3: lpc_spec_launch<3, M>(a, st); break;
-                        default: lpc_spec_launch<4, M>(a, st); break;
-                    }
-                    break;
-                }
-                if (a.s.C <= kLaMaxChains) {
-                    mcmc_note_step_kernel("lpc_rwm_la<%d, %s, %s>", NB, M::kName, us);
-                    if (a.s.scale_uniform) lpc_rwm_la<NB, M, true><<<1, kBlock, 0, st>>>(a);
-                    else lpc_rwm_la<NB, M, false><<<1, kBlock, 0, st>>>(a);
-                    break;
-                }
-                mcmc_note_step_kernel("lpc_rwm<%d, %s, %s, %s>", NB, b, M::kName, us);
-                {
-                    const dim3 g768((unsigned)((a.s.C + kLpcRwmThreads - 1) / kLpcRwmThreads));
-                    if (a.s.scale_uniform) lpc_rwm<NB, F, M, true><<<g768, kLpcRwmThreads, 0, st>>>(a);
-                    else lpc_rwm<NB, F, M, false><<<g768, kLpcRwmThreads, 0, st>>>(a);
-                }
-                break;
-            case SK_MALA:
-                mcmc_note_step_kernel("lpc_mala<%d, %s, %s>", NB, b, M::kName);
-                lpc_mala<NB, F, M><<<gridT(lpc_grad_threads<NB>()), lpc_grad_threads<NB>(), 0, st>>>(a);
-                break;
-            case SK_HMC:
-                mcmc_note_step_kernel("lpc_hmc<%d, %s, %s, false>", NB, b, M::kName);
-                lpc_hmc<NB, F, M, false><<<gridT(lpc_grad_threads<NB>()), lpc_grad_threads<NB>(), 0, st>>>(a);
-                break;
-            case SK_HMCDA:
-                mcmc_note_step_kernel("lpc_hmc<%d, %s, %s, true>", NB, b, M::kName);
-                lpc_hmc<NB, F, M, true><<<gridT(lpc_grad_threads<NB>()), lpc_grad_threads<NB>(), 0, st>>>(a);
-                break;
-            default: return hipErrorInvalidValue;
-        }
-    }
-    return hipGetLastError();
-}
-
-// SPEC: instantiate the FULL (d == 4 NB) variants too -- for the models the benchmarks run
-template <int NB, class M, bool SPEC>
-static hipError_t lpc_launch_nb(const KernelArgs& a, hipStream_t st) {
-    if (SPEC && a.s.d == 4 * NB) return lpc_launch_model<NB, SPEC, M>(a, st);
-    return lpc_launch_model<NB, false, M>(a, st);
-}
-
-template <class M, bool SPEC>
-static hipError_t lpc_step(const KernelArgs& a, hipStream_t st) {
-    switch ((a.s.d + 3) / 4) {
-        case 1: return lpc_launch_nb<1, M, SPEC>(a, st);
-        case 2: return lpc_launch_nb<2, M, SPEC>(a, st);
-        case 3: return lpc_launch_nb<3, M, SPEC>(a, st);
-        case 4: return lpc_launch_nb<4, M, SPEC>(a, st);
-        case 5: return lpc_launch_nb<5, M, SPEC>(a, st);
-        case 6: return lpc_launch_nb<6, M, SPEC>(a, st);
-        case 7: return lpc_launch_nb<7, M, SPEC>(a, st);
-        case 8: return lpc_launch_nb<8, M, SPEC>(a, st);
-        default: return hipErrorInvalidValue;
-    }
-}
-
-template <class M>
-static hipError_t lpc_eval_m(const KernelArgs& a, const double* xin, double* lp, double* g, int check,
-                             hipStream_t st) {
-    const dim3 grid((unsigned)((a.s.C + kBlock - 1) / kBlock));
-    const dim3 grid2((unsigned)((a.s.C + kBlock / 2 - 1) / (kBlock / 2)));       // PairChain: 128 chains a block
-    switch ((a.s.d + 3) / 4) {
-        case 1: lpc_eval<1, M><<<grid, kBlock, 0, st>>>(a, xin, lp, g, check); break;
-        case 2: lpc_eval<2, M><<<grid, kBlock, 0, st>>>(a, xin, lp, g, check); break;
-        case 3: lpc_eval<3, M><<<grid, kBlock, 0, st>>>(a, xin, lp, g, check); break;
-        case 4: lpc_eval<4, M><<<grid, kBlock, 0, st>>>(a, xin, lp, g, check); break;
-        case 5:
-        case 6: lpp_eval<3, M><<<grid2, kBlock, 0, st>>>(a, xin, lp, g, check); break;
-        case 7:
-        case 8: lpp_eval<4, M><<<grid2, kBlock, 0, st>>>(a, xin, lp, g, check); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
-
 // storeLeaps records (samplers.hpp hmc_record_body), generic mapping only: a diagnostic
 template <int NB, class M, bool DA>
 __global__ __launch_bounds__(kBlock) void lpc_hmc_rec(KernelArgs a, LeapRec r) { hmc_record_body<LaneChain<NB>, M, DA>(a, r); }
@@ -477,49 +338,94 @@ __global__ __launch_bounds__(kBlock) void lpp_hmc_rec(KernelArgs a, LeapRec r) {
     hmc_record_body<PairChain<NB, false, kBlock, kTabGlobal>, M, DA>(a, r);
 }
 
-template <class M>
-static hipError_t lpc_record_m(const KernelArgs& a, const LeapRec& r, hipStream_t st) {
-    const dim3 grid((unsigned)((a.s.C + kBlock - 1) / kBlock));
-    const dim3 grid2((unsigned)((a.s.C + kBlock / 2 - 1) / (kBlock / 2)));
-    const bool da = a.sa.kind == SK_HMCDA;
-#define LPC_REC(NB)                                                       \
-    case NB:                                                              \
-        if (da) lpc_hmc_rec<NB, M, true><<<grid, kBlock, 0, st>>>(a, r);   \
-        else lpc_hmc_rec<NB, M, false><<<grid, kBlock, 0, st>>>(a, r);     \
-        break;
-#define LPP_REC(NB, NBL)                                                    \
-    case NB:                                                                \
-        if (da) lpp_hmc_rec<NBL, M, true><<<grid2, kBlock, 0, st>>>(a, r);   \
-        else lpp_hmc_rec<NBL, M, false><<<grid2, kBlock, 0, st>>>(a, r);     \
-        break;
-    switch ((a.s.d + 3) / 4) {
-        LPC_REC(1) LPC_REC(2) LPC_REC(3) LPC_REC(4) LPP_REC(5, 3) LPP_REC(6, 3) LPP_REC(7, 4) LPP_REC(8, 4)
-        default: return hipErrorInvalidValue;
-    }
-#undef LPC_REC
-#undef LPP_REC
-    return hipGetLastError();
+// ------------------------------------------------------------------ launchers
+// Each launches the instance the plan names (layout_api.hpp for_int / for_bools / launch_inst; launch_plan.hpp
+// inst(map, body, n, threads, F, US, DA) restates it beside the kernel).  Out of reach at compile time: F on a model
+// without FULL instances, US beyond RWM, lpp NBL outside {3, 4}, lpc_rwm_spec outside 1..4.
+template <class M, int32_t MK>
+static hipError_t lpc_step(const KernelArgs& a, const LaunchPlan& p, hipStream_t st) {
+    constexpr bool FULL = unit_model<M, MK>().full_lane;
+    const KernelInstance& k = p.k;
+    const hipError_t e = for_bools(k.F, k.US, k.DA, [&](auto f, auto us, auto da) {
+        constexpr bool F = decltype(f)::value, US = decltype(us)::value, DA = decltype(da)::value;
+        if constexpr (F && !FULL) return hipErrorInvalidValue;
+        else if (k.body == B_RWM_SPEC)
+            return for_int<1, 2, 3, 4>(k.n, [&](auto d) {
+                constexpr int D = decltype(d)::value;
+                return launch_inst(p, inst(MAP_LPC, B_RWM_SPEC, D, kBlock, F, US, DA), lpc_rwm_spec<D, M, US>, st, a);
+            });
+        else if (k.body == B_RWM_LA)
+            return for_int<1, 2, 3, 4, 5, 6, 7, 8>(k.n, [&](auto nb) {    // d > 16: lpp_rwm's summation order
+                constexpr int NB = decltype(nb)::value;
+                return launch_inst(p, inst(MAP_LPC, B_RWM_LA, NB, kBlock, F, US, DA), lpc_rwm_la<NB, M, US>, st, a);
+            });
+        else if (k.map == MAP_LPC)
+            return for_int<1, 2, 3, 4>(k.n, [&](auto nb) {
+                constexpr int NB = decltype(nb)::value, T = lpc_grad_threads(NB);
+                switch (k.body) {
+                    case B_RWM:
+                        return launch_inst(p, inst(MAP_LPC, B_RWM, NB, kLpcRwmThreads, F, US, DA),
+                                           lpc_rwm<NB, F, M, US>, st, a);
+                    case B_MALA:
+                        return launch_inst(p, inst(MAP_LPC, B_MALA, NB, T, F, US, DA), lpc_mala<NB, F, M>, st, a);
+                    case B_HMC:
+                        return launch_inst(p, inst(MAP_LPC, B_HMC, NB, T, F, US, DA), lpc_hmc<NB, F, M, DA>, st, a);
+                    default: return hipErrorInvalidValue;
+                }
+            });
+        else
+            return for_int<3, 4>(k.n, [&](auto nbl) {
+                constexpr int NBL = decltype(nbl)::value, T = lpp_mala_threads(F);
+                switch (k.body) {
+                    case B_RWM:
+                        return launch_inst(p, inst(MAP_LPP, B_RWM, NBL, kPairThreads, F, US, DA),
+                                           lpp_rwm<NBL, F, M, US>, st, a);
+                    case B_MALA:
+                        return launch_inst(p, inst(MAP_LPP, B_MALA, NBL, T, F, US, DA), lpp_mala<NBL, F, M>, st, a);
+                    case B_HMC:
+                        return launch_inst(p, inst(MAP_LPP, B_HMC, NBL, kPairThreads, F, US, DA),
+                                           lpp_hmc<NBL, F, M, DA>, st, a);
+                    default: return hipErrorInvalidValue;
+                }
+            });
+    });
+    return note_launched(e, p, M::kName);
 }
 
-}  // namespace mcmc
+template <class M>
+static hipError_t lpc_eval_m(const KernelArgs& a, const LaunchPlan& p, const double* xin, double* lp, double* g,
+                             int check, hipStream_t st) {
+    if (p.k.map == MAP_LPC)
+        return for_int<1, 2, 3, 4>(p.k.n, [&](auto nb) {
+            constexpr int NB = decltype(nb)::value;
+            return launch_inst(p, inst(MAP_LPC, B_EVAL, NB, kBlock), lpc_eval<NB, M>, st, a, xin, lp, g, check);
+        });
+    return for_int<3, 4>(p.k.n, [&](auto nbl) {
+        constexpr int NBL = decltype(nbl)::value;
+        return launch_inst(p, inst(MAP_LPP, B_EVAL, NBL, kBlock), lpp_eval<NBL, M>, st, a, xin, lp, g, check);
+    });
+}
 
-// one translation unit per model: LPC_UNIT(iso, IsoDot, true) defines mcmc_lpc_step_iso / mcmc_lpc_eval_iso
-#define LPC_UNIT(name, Model, SPEC)                                                                      \
-    hipError_t mcmc_lpc_step_##name(const mcmc::KernelArgs& a, hipStream_t st) {                         \
-        return mcmc::lpc_step<mcmc::Model, SPEC>(a, st);                                                \
-    }                                                                                                    \
-    hipError_t mcmc_lpc_eval_##name(const mcmc::KernelArgs& a, const double* xin, double* lp, double* g, \
-                                    int check, hipStream_t st) {                                         \
-        return mcmc::lpc_eval_m<mcmc::Model>(a, xin, lp, g, check, st);                                 \
-    }                                                                                                    \
-    hipError_t mcmc_lpc_record_##name(const mcmc::KernelArgs& a, const mcmc::LeapRec& r, hipStream_t st) { \
-        return mcmc::lpc_record_m<mcmc::Model>(a, r, st);                                               \
-    }
+template <class M>
+static hipError_t lpc_record_m(const KernelArgs& a, const LaunchPlan& p, const LeapRec& r, hipStream_t st) {
+    return for_bool(p.k.DA, [&](auto da) {
+        constexpr bool DA = decltype(da)::value;
+        if (p.k.map == MAP_LPC)
+            return for_int<1, 2, 3, 4>(p.k.n, [&](auto nb) {
+                constexpr int NB = decltype(nb)::value;
+                return launch_inst(p, inst(MAP_LPC, B_HMC_REC, NB, kBlock, false, false, DA),
+                                   lpc_hmc_rec<NB, M, DA>, st, a, r);
+            });
+        return for_int<3, 4>(p.k.n, [&](auto nbl) {
+            constexpr int NBL = decltype(nbl)::value;
+            return launch_inst(p, inst(MAP_LPP, B_HMC_REC, NBL, kBlock, false, false, DA),
+                               lpp_hmc_rec<NBL, M, DA>, st, a, r);
+        });
+    });
+}
 
 // RAM kernels live in their own translation units (lpc_ram_*.hip, built without machine LICM: hoisted
-// fp64 constants would pin the scalar file the factor addressing needs); LPC_RAM_UNIT(iso, IsoDot)
-// defines mcmc_lpc_ram_iso.
-namespace mcmc {
+// fp64 constants would pin the scalar file the factor addressing needs).
 template <int NB, class M>
 // d > 16: the log-target in PairChain's order (LaneChain SPLIT), as the chains' model.eval (lpp_eval) forms it.
 // The next step's rvec from LDS (ram_body kZLds) and the Box-Muller tables from LDS too, except at 12 < d <= 16,
@@ -529,25 +435,22 @@ __global__ __launch_bounds__(kBlock, NB <= 4 ? 2 : 1) void lpc_ram(KernelArgs a)
 }
 
 template <class M>
-static hipError_t lpc_ram_step(const KernelArgs& a, hipStream_t st) {
-    const dim3 grid((unsigned)((a.s.C + kBlock - 1) / kBlock));
-    mcmc_note_step_kernel("lpc_ram<%d, %s>", (a.s.d + 3) / 4, M::kName);
-    switch ((a.s.d + 3) / 4) {
-        case 1: lpc_ram<1, M><<<grid, kBlock, 0, st>>>(a); break;
-        case 2: lpc_ram<2, M><<<grid, kBlock, 0, st>>>(a); break;
-        case 3: lpc_ram<3, M><<<grid, kBlock, 0, st>>>(a); break;
-        case 4: lpc_ram<4, M><<<grid, kBlock, 0, st>>>(a); break;
-        case 5: lpc_ram<5, M><<<grid, kBlock, 0, st>>>(a); break;
-        case 6: lpc_ram<6, M><<<grid, kBlock, 0, st>>>(a); break;
-        case 7: lpc_ram<7, M><<<grid, kBlock, 0, st>>>(a); break;
-        case 8: lpc_ram<8, M><<<grid, kBlock, 0, st>>>(a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+static hipError_t lpc_ram_step(const KernelArgs& a, const LaunchPlan& p, hipStream_t st) {
+    const hipError_t e = for_int<1, 2, 3, 4, 5, 6, 7, 8>(p.k.n, [&](auto nb) {
+        constexpr int NB = decltype(nb)::value;
+        return launch_inst(p, inst(MAP_LPC, B_RAM, NB, kBlock), lpc_ram<NB, M>, st, a);
+    });
+    return note_launched(e, p, M::kName);
 }
+
 }  // namespace mcmc
 
-#define LPC_RAM_UNIT(name, Model)                                                \
-    hipError_t mcmc_lpc_ram_##name(const mcmc::KernelArgs& a, hipStream_t st) { \
-        return mcmc::lpc_ram_step<mcmc::Model>(a, st);                          \
+// one translation unit per model: LPC_UNIT(iso, IsoDot, MK_ISO) defines the unit mcmc::lpc_iso (layout_api.hpp);
+// LPC_RAM_UNIT(iso, IsoDot) defines mcmc::lpc_ram_iso
+#define LPC_UNIT(name, Model, MK)                                                                        \
+    mcmc::KernelUnit mcmc::lpc_##name() {                                                                \
+        return {lpc_step<Model, MK>, lpc_eval_m<Model>, lpc_record_m<Model>};                            \
     }
+#define LPC_RAM_UNIT(name, Model) \
+    mcmc::KernelUnit mcmc::lpc_ram_##name() { return {lpc_ram_step<Model>, nullptr, nullptr}; }
+

@@ -1,20 +1,19 @@
-// nuts.hip -- dispatch of the NUTS kernels (nuts.hpp, nuts_impl.hpp) on the model kind: the step loop (init == 0) or
-// the initial epsilon search (init != 0).  Built for the lane-per-chain and two-lanes-per-chain targets, d <= 32.
+// nuts.hip -- the unit table of the NUTS kernels (nuts.hpp, nuts_impl.hpp): the step loop (init == 0) or the initial
+// epsilon search (init != 0).  Built for the lane-per-chain and two-lanes-per-chain targets, d <= 32.
 #include "layout_api.hpp"
 
-hipError_t mcmc_launch_nuts(const mcmc::KernelArgs& a, int init, hipStream_t st) {
-    using namespace mcmc;
-    if (a.s.d < 1 || a.s.d > mcmc_nuts_max_d()) return hipErrorInvalidValue;
-    switch (a.m.kind) {
-        case MK_ISO: return mcmc_nuts_iso(a, init, st);
-        case MK_NORMAL: return mcmc_nuts_normal(a, init, st);
-        case MK_ABS_NORMAL: return mcmc_nuts_absnormal(a, init, st);
-        case MK_DIST: return mcmc_nuts_dist(a, init, st);
-        case MK_DIST_OBS: return mcmc_nuts_distobs(a, init, st);
-        case MK_OU: return mcmc_nuts_ou(a, init, st);
-        default: return hipErrorInvalidValue;
-    }
+using namespace mcmc;
+
+static const UnitRow kNutsUnits[] = {
+    {MK_ISO, nuts_iso, nullptr},   {MK_NORMAL, nuts_normal, nullptr},     {MK_ABS_NORMAL, nuts_absnormal, nullptr},
+    {MK_DIST, nuts_dist, nullptr}, {MK_DIST_OBS, nuts_distobs, nullptr},  {MK_OU, nuts_ou, nullptr},
+};
+
+hipError_t mcmc_launch_nuts(const KernelArgs& a, int init, hipStream_t st) {
+    LaunchPlan p;
+    const KernelUnit u = unit_for(kNutsUnits, a, init ? OP_NUTS_INIT : OP_STEP, false, p);
+    return u.step ? u.step(a, p, st) : hipErrorInvalidValue;
 }
 
-int mcmc_nuts_max_d() { return 32; }
+int mcmc_nuts_max_d() { return kNutsMaxD; }
 int mcmc_nuts_max_doublings() { return 10; }

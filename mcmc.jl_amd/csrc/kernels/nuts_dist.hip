@@ -1,3 +1,3 @@
 // NUTS kernels of one model (nuts_impl.hpp); separate units compile in parallel
 #include "nuts_impl.hpp"
-NUTS_UNIT(dist, DistDSL, 8)
+NUTS_UNIT(dist, DistDSL, MK_DIST)

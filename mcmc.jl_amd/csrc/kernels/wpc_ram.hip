@@ -17,37 +17,21 @@ __global__ __launch_bounds__(kBlock) void wpc_ram(KernelArgs a) { ram_wave_body<
 template <int G, class M>
 __global__ __launch_bounds__(kBlock, 3) void wpc_ram2(KernelArgs a) { ram_wave_body<HalfWaveChain<G>, M>(a); }
 
-constexpr int kRamHalfMaxD = 256;
-
 template <class M>
-static hipError_t wpc_ram_step(const KernelArgs& a, hipStream_t st) {
-    if (a.s.d <= kRamHalfMaxD) {
-        constexpr int cpb = 2 * kChainsPerBlock;
-        const dim3 grid((unsigned)((a.s.C + cpb - 1) / cpb));
-        const int g = a.s.d <= 128 ? 1 : 2;
-        mcmc_note_step_kernel("wpc_ram2<%d, %s>", g, M::kName);
-        if (g == 1) wpc_ram2<1, M><<<grid, kBlock, 0, st>>>(a);
-        else wpc_ram2<2, M><<<grid, kBlock, 0, st>>>(a);
-        return hipGetLastError();
-    }
-    const dim3 grid((unsigned)((a.s.C + kChainsPerBlock - 1) / kChainsPerBlock));
-    const int g = wpc_nb_for(a.s.d);
-    mcmc_note_step_kernel("wpc_ram<%d, %s>", g, M::kName);
-    switch (g) {
-        case 2: wpc_ram<2, M><<<grid, kBlock, 0, st>>>(a); break;
-        case 4: wpc_ram<4, M><<<grid, kBlock, 0, st>>>(a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+static hipError_t wpc_ram_step(const KernelArgs& a, const LaunchPlan& p, hipStream_t st) {
+    const hipError_t e = p.k.body == B_RAM2 ? for_int<1, 2>(p.k.n, [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        return launch_inst(p, inst(MAP_WPC, B_RAM2, G, kBlock), wpc_ram2<G, M>, st, a);
+    }) : for_int<2, 4>(p.k.n, [&](auto g) {
+        constexpr int G = decltype(g)::value;
+        return launch_inst(p, inst(MAP_WPC, B_RAM, G, kBlock), wpc_ram<G, M>, st, a);
+    });
+    return note_launched(e, p, M::kName);
 }
+
+KernelUnit wpc_ram_iso() { return {wpc_ram_step<IsoDot>, nullptr, nullptr}; }
+KernelUnit wpc_ram_normal() { return {wpc_ram_step<NormalDSL>, nullptr, nullptr}; }
+KernelUnit wpc_ram_absnormal() { return {wpc_ram_step<AbsNormalDSL>, nullptr, nullptr}; }
+KernelUnit wpc_ram_dist() { return {wpc_ram_step<DistDSL>, nullptr, nullptr}; }
 
 }  // namespace mcmc
-
-hipError_t mcmc_wpc_ram_iso(const mcmc::KernelArgs& a, hipStream_t st) { return mcmc::wpc_ram_step<mcmc::IsoDot>(a, st); }
-hipError_t mcmc_wpc_ram_normal(const mcmc::KernelArgs& a, hipStream_t st) {
-    return mcmc::wpc_ram_step<mcmc::NormalDSL>(a, st);
-}
-hipError_t mcmc_wpc_ram_absnormal(const mcmc::KernelArgs& a, hipStream_t st) {
-    return mcmc::wpc_ram_step<mcmc::AbsNormalDSL>(a, st);
-}
-hipError_t mcmc_wpc_ram_dist(const mcmc::KernelArgs& a, hipStream_t st) { return mcmc::wpc_ram_step<mcmc::DistDSL>(a, st); }
