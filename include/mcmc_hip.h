@@ -412,6 +412,43 @@ int mcmc_run_seqmc(mcmc_chains* const* targets, int32_t ntargets, int64_t npart,
                    const mcmc_seqmc_cfg* cfg, uint64_t seed, int32_t on_device, double* samples, double* weights,
                    int32_t* resampled, double* runtime_s);
 
+/* ---- SerialTempMC serial-tempering runner (src/runners/SerialTempMC.jl:16-85) ----
+ * targets[t] (2 <= ntargets) are chain batches of one context with equal d, chain offset and nchains == nwalkers:
+ * walker c is chain c of every target, an independent run_serialtempmc keyed by its global chain id.  A walker holds
+ * the fields run_serialtempmc reads of its last MCMCSample s (samplers.jl:10-18): s.ppars, the position its task
+ * stands at, which is what is stored (SerialTempMC.jl:77); s.pars and s.logtarget, the position and log-target
+ * before that step, which is what a swap resets the other task to and compares (SerialTempMC.jl:62-64).
+ * It starts on targets[0] with one step from that batch's current state (SerialTempMC.jl:51).  Step i = 1..steps:
+ *   i % swap_period == 0: at2 = r >= at ? r + 1 : r with r = min(K - 2, floor(u (K - 1))); target at2 is reset to
+ *     s.pars (position, then lp and gradient by the eval kernel) and takes one step, s2; the swap is accepted iff
+ *     u2 < exp(((s.logtarget - s2.logtarget) + logW[at2]) - logW[at]), each operation rounded once, a NaN rejecting.
+ *     Accepted: at = at2, s = s2.  Rejected: the walker keeps at and s; its task is not consumed.
+ *   otherwise: s = one step of target `at` from s.ppars.
+ * For i > burnin, s.ppars, at (zero-based) and the swap-accepted bit are stored.  u = uniform52(w0, w1) and
+ * u2 = uniform52(w2, w3) of the Philox block (global chain id, i, 0, tag 8) under `seed`; each target's sampler draws
+ * come from its own batch's key and step counter.  On the device every target resets to the walkers' positions and
+ * steps all its chains on every step, and walker c takes the sample of its target: the step counter of every target
+ * advances by steps (targets[0]: steps + 1), its evaluation count as under mcmc_run_seqmc, the tuners see burnin 0
+ * (tuned MALA / HMC and HMCDA do not adapt), and RAM's factor of (target, walker) adapts on every step.  A sampler
+ * mcmc_run_seqmc refuses is refused here for the same reason (MCMC_E_UNSUPPORTED).
+ *   logW      : host [ntargets] log-weights of the targets, or NULL for zeros (SerialTempMC.jl:49; the reference's
+ *               adaptation is a TODO, SerialTempMC.jl:71)
+ *   samples   : [steps-burnin][d][nwalkers], or NULL
+ *   models    : [steps-burnin][nwalkers] int32 (the reference's commented res.misc[:mod]), or NULL
+ *   swap_bits : [steps-burnin][ceil(nwalkers/64)] uint64, walker c in bit c % 64 of word c / 64, or NULL
+ *   final_at  : [nwalkers] int32, the walkers' targets after the last step, or NULL
+ * on_device != 0: samples/models/swap_bits/final_at are device pointers on the context's GPU. */
+typedef struct {
+    int64_t steps;           /* SerialTempMC.steps (SerialTempMC.jl:17)                               */
+    int64_t burnin;          /* SerialTempMC.burnin                                                   */
+    int64_t swap_period;     /* SerialTempMC.swapPeriod: a swap is proposed when i % swap_period == 0 */
+} mcmc_serialtempmc_cfg;
+int mcmc_serialtempmc_validate(const mcmc_serialtempmc_cfg* cfg);
+int mcmc_run_serialtempmc(mcmc_chains* const* targets, int32_t ntargets, int64_t nwalkers,
+                          const mcmc_serialtempmc_cfg* cfg, const double* logW, uint64_t seed, int32_t on_device,
+                          double* samples, int32_t* models, uint64_t* swap_bits, int32_t* final_at,
+                          double* runtime_s);
+
 /* ---- output analysis (src/stats/ess.jl:6-10, var.jl:7-117) ----
  * Effective sample size n * var_iid / var_vtype of every (parameter j, chain c) series of
  * samples [nkept][d][nchains] (the mcmc_outputs layout).  vtype: MCMC_VAR_IMSE (Geyer initial

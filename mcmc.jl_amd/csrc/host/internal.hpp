@@ -188,6 +188,9 @@ struct RunRange {
 mcmc::KernelArgs step_args(const mcmc_chains* c, const RunRange& r);
 // the step kernels of one launch: the only place that maps a sampler kind to its step launcher
 hipError_t launch_chain_step(const mcmc_chains* c, const mcmc::KernelArgs& a, hipStream_t st);
+// one sampler step of every chain of c from its current state, nothing kept, the tuners' burnin 0: the `consume` of
+// the population runners (seqmc_stats.cpp; SeqMC.jl:69, SerialTempMC.jl:63,68)
+int step_once(mcmc_chains* c, hipStream_t st);
 // forget the step kernel noted on this thread (kernels_api.hpp mcmc_note_step_kernel; context.cpp)
 void mcmc_clear_step_kernel();
 // mcmc_run_serialmc with host outputs of a larger batch: rows ldc chains apart (run.cpp)

@@ -84,6 +84,17 @@ hipError_t mcmc_seqmc_resample(int64_t N, int d, const double* cp, const int32_t
                                double* logtarget_out, double* logW, hipStream_t st);
 hipError_t mcmc_seqmc_store(int64_t N, int d, const double* pars, const double* logW, double* samples, double* weights,
                             hipStream_t st);
+// SerialTempMC walker bookkeeping (stemp.hip): every array is [..][C] over the walkers; chain0 the first walker's
+// global chain id, step the runner step, seed the run's Philox key.  x: a target's positions as columns, row stride ldx
+hipError_t mcmc_stemp_pick(int64_t C, int32_t K, uint32_t chain0, uint64_t seed, uint32_t step, int32_t is_swap,
+                           const int32_t* at, int32_t* tgt, hipStream_t st);
+hipError_t mcmc_stemp_take(int64_t C, int d, int32_t t, const int32_t* tgt, const double* x, int64_t ldx,
+                           const double* ll0, double* cand, double* cand_lt, hipStream_t st);
+hipError_t mcmc_stemp_swap(int64_t C, int d, uint32_t chain0, uint64_t seed, uint32_t step, int32_t is_swap,
+                           const double* logW, int32_t* at, const int32_t* tgt, double* cur, double* prev, double* lt,
+                           const double* cand, const double* cand_lt, int32_t* swapped, hipStream_t st);
+hipError_t mcmc_stemp_store(int64_t C, int d, const double* cur, const int32_t* at, const int32_t* swapped,
+                            double* samples, int32_t* models, uint64_t* bits, hipStream_t st);
 // effective sample size of every (parameter, chain) series of samples [n][d][C] (stats.hip)
 hipError_t mcmc_launch_ess(const double* samples, int64_t n, int64_t d, int64_t C, int32_t vtype, int64_t maxlag,
                            int64_t batchlen, double* ess, double* var, hipStream_t st);

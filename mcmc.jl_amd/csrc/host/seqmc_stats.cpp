@@ -23,7 +23,7 @@ extern "C" int mcmc_seqmc_validate(const mcmc_seqmc_cfg* cfg) {
 
 // One sampler step of every chain of `c` from its current state, nothing kept (the SamplerTask's
 // `consume` inside run_seqmc, SeqMC.jl:69).
-static int step_once(mcmc_chains* c, hipStream_t st) {
+int step_once(mcmc_chains* c, hipStream_t st) {
     KernelArgs a = step_args(c, {0, 1, 1, 0});             // a run of one step, nothing kept; the tuners' burnin 0
     a.s.step_begin = c->steps_done + 1;
     a.s.nsteps = 1;

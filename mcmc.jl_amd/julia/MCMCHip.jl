@@ -124,6 +124,37 @@ function run_serialmc(ch, d, C; steps, burnin = 0, thinning = 1)
     smp, accept, out.runtime_s
 end
 
+# SerialTempMC (SerialTempMC.jl:16-85): nwalkers serial-tempering walkers as one batch; targets are chain batches of
+# nwalkers chains each (chains(model, s, nwalkers; seed = ...), one seed per target), walker c chain c of each.
+struct SerialTempMCCfg
+    steps::Int64
+    burnin::Int64
+    swap_period::Int64
+end
+serialtempmc_validate(cfg::SerialTempMCCfg) =
+    check(ccall((:mcmc_serialtempmc_validate, lib), Cint, (Ref{SerialTempMCCfg},), cfg))
+
+# returns samples (nwalkers, d, steps - burnin), the one-based target index of every stored step (nwalkers,
+# steps - burnin), whether that step accepted a swap, the walkers' final targets and the run time
+function run_serialtempmc(targets::Vector{Ptr{Cvoid}}, d, nwalkers; steps = 1, burnin = 0, swapPeriod = 5,
+                          logW = nothing, seed = 1)
+    cfg = SerialTempMCCfg(steps, burnin, swapPeriod)
+    nst = steps - burnin
+    smp = Array{Float64}(undef, nwalkers, d, max(nst, 0))
+    mod = zeros(Int32, nwalkers, max(nst, 0))
+    bits = zeros(UInt64, cld(nwalkers, 64), max(nst, 0))
+    final = zeros(Int32, nwalkers)
+    rt = Ref{Float64}(0.0)
+    wv = logW === nothing ? Float64[] : convert(Vector{Float64}, logW)
+    w = logW === nothing ? Ptr{Float64}(C_NULL) : pointer(wv)
+    GC.@preserve wv check(ccall((:mcmc_run_serialtempmc, lib), Cint,
+        (Ptr{Ptr{Cvoid}}, Int32, Int64, Ref{SerialTempMCCfg}, Ptr{Float64}, UInt64, Int32, Ptr{Float64}, Ptr{Int32},
+         Ptr{UInt64}, Ptr{Int32}, Ref{Float64}),
+        targets, length(targets), nwalkers, cfg, w, seed, 0, smp, mod, bits, final, rt))
+    swap = [(bits[fld(c, 64) + 1, j] >> (c % 64)) & 1 == 1 for c in 0:nwalkers-1, j in 1:max(nst, 0)]
+    smp, mod .+ Int32(1), swap, final .+ Int32(1), rt[]
+end
+
 # linearZv / quadraticZv (zv.jl:8-68) of every chain: samples and gradients of size (C, d, nkept) -> the ZV chains
 # (C, d, nkept), the coefficients (C, d, k) and info (C; nonzero: the chain's Gram matrix is not positive definite)
 function stats_zv(ctx, smp::Array{Float64,3}, grd::Array{Float64,3}; order = 1)

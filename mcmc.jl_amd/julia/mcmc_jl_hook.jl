@@ -22,6 +22,9 @@
 #                                                  With SeqMC runners, GPU targets run as one mcmc_run_seqmc (one
 #                                                  chain batch per target, a chain per particle) instead of
 #                                                  run_seqmc's reset + consume per particle (SeqMC.jl:39-122);
+#                                                  with SerialTempMC runners, GPU targets run as one
+#                                                  mcmc_run_serialtempmc (hip_run_serialtempmc: nwalkers walkers a
+#                                                  batch) instead of run_serialtempmc's one-step launches;
 #   prun(t::Array{MCMCTask})    runners.jl:35-42 -- redefined likewise: like GPU tasks as one batch split over every
 #                                                  visible GPU (mcmc_group_*), then stopped (run_serialmc_exit);
 #                                                  other arrays pmap as before;
@@ -71,6 +74,9 @@ type HipOutputs                   # mcmc_outputs (the library writes runtime_s, 
 end
 immutable HipSeqMCCfg             # mcmc_seqmc_cfg
   steps::Int64; burnin::Int64; trigger::Float64
+end
+immutable HipSerialTempMCCfg      # mcmc_serialtempmc_cfg
+  steps::Int64; burnin::Int64; swap_period::Int64
 end
 
 const HIP_MODEL_KINDS = {:isonormal_dot => 1, :normal => 2, :logistic => 3, :linear => 4, :absnormal => 5, :dist => 6,
@@ -611,6 +617,7 @@ function run(t::Array{MCMCTask}; args...)
     for i in 1:length(t); res[i] = run(t[i]); end
     return res
   end
+  isa(lastrunner, SerialTempMC) && hip_seqmc_able(t) && return hip_run_serialtempmc(t; args...)
   isa(lastrunner, SerialTempMC) && return run_serialtempmc(t)
   run_seqmc(t; args...)
 end
@@ -673,6 +680,43 @@ function hip_run_seqmc(targets::Array{MCMCTask}; particles::Vector{Vector{Float6
   end
   MCMCChain((r.burnin + 1):1:((r.steps - r.burnin) * npart), DataFrame(M, hip_colnames(targets[end].model)),
             DataFrame(), {"weigths" => vec(W), "particle" => rep([1:npart], nst), "resampled" => F'}, targets, rt[1])
+end
+
+# ---- SerialTempMC (SerialTempMC.jl:31-85) on the GPU: arrays of GPU targets the library runs under SeqMC too
+# (hip_seqmc_able: none started, no NUTS / ERMLMC / RMLMC; the library refuses the other metric-tensor samplers itself).
+# run_serialtempmc(tasks) as one mcmc_run_serialtempmc: walker c is chain c of every target's chain batch; the pick of
+# the other task, its reset to the walker's s.pars, the swap test and the store run on the device.  nwalkers = 1 is
+# the reference's run: one MCMCChain, range 1:1:2 and samples steps - burnin rows as the reference builds it
+# (SerialTempMC.jl:47), with diagnostics "mod" (the reference's commented res.misc[:mod], one-based) and "swap".  More
+# walkers stack walker-major: rows (w - 1) * (steps - burnin) + 1 ... of walker w, and "walker" names them.  logW: the
+# tasks' log-weights (zeros, SerialTempMC.jl:49).  The walkers' chains and their swap draws come from the global stream.
+function hip_run_serialtempmc(tasks::Array{MCMCTask}; nwalkers::Int = 1, logW::Vector{Float64} = zeros(length(tasks)))
+  nmods = length(tasks)
+  tsize = tasks[end].model.size
+  r = tasks[end].runner
+  @assert all(map(t -> t.model.size, tasks) .== tsize) "Models do not have the same parameter vector size"
+  @assert length(logW) == nmods "logW must have one entry per task"
+  seed, first = hip_draw(nwalkers)
+  chs = HipChains[HipChains(hip_model_handle(tasks[k].model), hip_sampler(tasks[k].sampler), tsize, nwalkers,
+                            hip_target_key(seed, k - 1), first) for k in 1:nmods]
+  nst = r.steps - r.burnin
+  S = Array(Float64, nwalkers, tsize, nst)                               # [nst][d][nwalkers]
+  A = zeros(Int32, nwalkers, nst)                                        # [nst][nwalkers]
+  B = zeros(Uint64, div(nwalkers + 63, 64), nst)                         # [nst][ceil(nwalkers / 64)]
+  F = zeros(Int32, nwalkers)
+  rt = Array(Float64, 1)
+  hipcheck(ccall((:mcmc_run_serialtempmc, hiplib), Cint,
+                 (Ptr{Ptr{Void}}, Int32, Int64, Ptr{HipSerialTempMCCfg}, Ptr{Float64}, Uint64, Int32, Ptr{Float64},
+                  Ptr{Int32}, Ptr{Uint64}, Ptr{Int32}, Ptr{Float64}),
+                 Ptr{Void}[c.h for c in chs], nmods, nwalkers, [HipSerialTempMCCfg(r.steps, r.burnin, r.swapPeriod)],
+                 logW, seed, 0, S, A, B, F, rt))
+  M = Array(Float64, nwalkers * nst, tsize)
+  for w in 1:nwalkers, i in 1:nst, j in 1:tsize
+    M[(w - 1) * nst + i, j] = S[w, j, i]
+  end
+  swap = Bool[(B[div(w - 1, 64) + 1, i] >> ((w - 1) % 64)) & 1 == 1 for i in 1:nst, w in 1:nwalkers]
+  MCMCChain(1:1:2, DataFrame(M, hip_colnames(tasks[end].model)), DataFrame(),
+            {"mod" => vec(A') .+ 1, "swap" => vec(swap), "walker" => rep([1:nwalkers], each = nst)}, tasks, rt[1])
 end
 
 # ---- ESS on the device (ess.jl:6-10 with var.jl's IMSE / IPSE / batch means; mcmc_stats_ess)

@@ -76,7 +76,7 @@ EXPORTED_SYMBOLS = (
     "mcmc_group_chains_set_steps_per_launch", "mcmc_group_chains_block", "mcmc_group_run_serialmc",
     "mcmc_group_last_pin_s",
     "mcmc_debug_group_inject_failure",
-    "mcmc_seqmc_validate", "mcmc_run_seqmc", "mcmc_stats_ess", "mcmc_stats_describe", "mcmc_stats_zv",
+    "mcmc_seqmc_validate", "mcmc_run_seqmc", "mcmc_serialtempmc_validate", "mcmc_run_serialtempmc", "mcmc_stats_ess", "mcmc_stats_describe", "mcmc_stats_zv",
     "mcmc_debug_detmath", "mcmc_debug_philox",
     "mcmc_debug_mfma_f64", "mcmc_debug_chains_order",
 )
@@ -203,6 +203,10 @@ def load() -> ct.CDLL:
         "mcmc_seqmc_validate": (ct.c_int, [ct.c_void_p]),
         "mcmc_run_seqmc": (ct.c_int, [ct.POINTER(ct.c_void_p), i32, i64, ct.c_void_p, ct.c_void_p, u64, i32,
                                       ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.POINTER(ct.c_double)]),
+        "mcmc_serialtempmc_validate": (ct.c_int, [ct.c_void_p]),
+        "mcmc_run_serialtempmc": (ct.c_int, [ct.POINTER(ct.c_void_p), i32, i64, ct.c_void_p, ct.c_void_p, u64, i32,
+                                             ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p,
+                                             ct.POINTER(ct.c_double)]),
         "mcmc_stats_ess": (ct.c_int, [P, ct.c_void_p, i64, i64, i64, i32, i64, i64, i32, ct.c_void_p,
                                       ct.c_void_p]),
         "mcmc_stats_describe": (ct.c_int, [P, ct.c_void_p, i64, i64, i64, i64, i32, ct.c_void_p, ct.c_void_p, i32,

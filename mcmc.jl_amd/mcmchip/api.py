@@ -808,8 +808,9 @@ class MCMCTask:
         self._group = None
         self._fork = None            # (batch task, first chain): chains of a batched run(Array), forked on first use
         self._stopped = False        # prun's tasks (run_serialmc_exit: stop!, SerialMC.jl:87-91)
-        if not isinstance(runner, SerialMC) and type(runner).__name__ != "SeqMC":
-            raise NotImplementedError("runners: SerialMC (one batch) or SeqMC (lists of targets, run_seqmc)")
+        if not isinstance(runner, SerialMC) and type(runner).__name__ not in ("SeqMC", "SerialTempMC"):
+            raise NotImplementedError("runners: SerialMC (one batch), or SeqMC / SerialTempMC (lists of targets, "
+                                      "run_seqmc / run_serialtempmc)")
         if sampler.uses_gradient and not model.has_gradient:
             name = type(sampler).__name__
             raise AssertionError(f"{name} sampler requires model with gradient function")
@@ -1204,6 +1205,11 @@ def run(t, *args, nchains: Optional[int] = None, seed: Optional[int] = None, **k
         if next(iter(kinds)).__name__ == "SeqMC":                 # run(t::Array{MCMCTask}) -> run_seqmc
             from .seqmc import run_seqmc
             return run_seqmc(t, seed=1 if seed is None else seed, **kw)
+        if next(iter(kinds)).__name__ == "SerialTempMC":          # runners.jl:27-28 -> run_serialtempmc
+            from .serialtemp import run_serialtempmc
+            if nchains is not None:
+                kw.setdefault("nwalkers", nchains)
+            return run_serialtempmc(t, seed=1 if seed is None else seed, **kw)
         if nchains is None and seed is None and not kw and all(_same_task_kind(x, t[0]) for x in t):
             return _run_batched(list(t))
         return [run(x, nchains=nchains, seed=seed, **kw) for x in t]
@@ -1246,6 +1252,13 @@ def resume(c, steps: int = 100, seed: Optional[int] = None, chain_offset: Option
     """resume(chain; steps) (SerialMC.jl:93-97): run(t.model, t.sampler, SerialMC(steps, thinning)) -- a *new*
     task from model.init.  Its chains are drawn from the global stream (the reference's new task samples on from the
     advanced global RNG), so they are not a replay of the original run; seed / chain_offset name them outright."""
+    if isinstance(c, MCMCChain) and isinstance(c.task, (list, tuple)):      # the one chain of a runner over targets
+        c = c.task
+    if isinstance(c, (list, tuple)) and c and type(c[-1].runner if isinstance(c[-1], MCMCTask)
+                                                   else c[-1].task.runner).__name__ == "SerialTempMC":
+        from .serialtemp import resume_serialtempmc            # runners.jl:63-64
+        kw = {} if seed is None else {"seed": seed}
+        return resume_serialtempmc([x if isinstance(x, MCMCTask) else x.task for x in c], steps=steps, **kw)
     if isinstance(c, (list, tuple)):
         return [resume(x, steps=steps, seed=seed, chain_offset=chain_offset) for x in c]
     t = c.task if isinstance(c, MCMCChain) else c
