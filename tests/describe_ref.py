@@ -8,48 +8,22 @@ from __future__ import annotations
 
 import ctypes as ct
 import functools
-import os
-import re
-import shlex
-import subprocess
 
 import numpy as np
 
-import oracle_ref as orc
+import checker_build
 import ess_cases as ec
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "describe_oracle.c")
-BUILD_DIR = os.path.join(HERE, "_build")
-LIB = os.path.join(BUILD_DIR, "libdescribe_oracle.so")
 NPOOLED = 6
 PROBS = (0.0, 0.025, 0.25, 0.5, 0.75, 0.975, 1.0)
 
 _lib = None
 
 
-def _make_vars():
-    text = open(os.path.join(orc.ORACLE_DIR, "Makefile")).read()
-    cc = re.search(r"^CC\s*\?=\s*(.+)$", text, re.M).group(1).strip()
-    cflags = re.search(r"^CFLAGS\s*:=\s*(.+)$", text, re.M).group(1).strip()
-    return os.environ.get("CC", cc), shlex.split(cflags)
-
-
-def build() -> None:
-    cc, cflags = _make_vars()
-    os.makedirs(BUILD_DIR, exist_ok=True)
-    tmp = LIB + f".{os.getpid()}.tmp"
-    subprocess.run([cc, *cflags, "-shared", "-o", tmp, SRC, "-lm"], check=True, cwd=HERE)
-    os.replace(tmp, LIB)
-
-
 def lib():
     global _lib
     if _lib is None:
-        newest = max(os.path.getmtime(SRC), os.path.getmtime(os.path.join(orc.ORACLE_DIR, "oracle.c")))
-        if not os.path.exists(LIB) or newest > os.path.getmtime(LIB):
-            build()
-        L = ct.CDLL(LIB)
+        L = checker_build.load("describe_oracle.c", "libdescribe_oracle.so")
         i64, D = ct.c_int64, ct.c_void_p
         L.orc_describe.restype = ct.c_int
         L.orc_describe.argtypes = [D, i64, i64, i64, i64, D, D, ct.c_int32, D, D]

@@ -2,9 +2,10 @@
 literal numpy transcription of both samplers (ERMLMC.jl:84-179, RMLMC.jl:89-179) driven by the build's draws."""
 import numpy as np
 
-import lmc_ref as lr
+import manifold_ref as lr
 import pmala_cases as pc
-import smmala_ref as sr
+
+sr = lr          # the tensor is the same checker's
 
 
 def literal_C(dG):
@@ -59,7 +60,7 @@ def literal(m, sp, C, steps, seed, burnin):
                 nLeaps, leapStep = t_nLeaps, t_leapStep
             else:
                 nLeaps, leapStep = sp.nLeaps, sp.leapStep
-            z, u_acc, u_leaps = lr.draws(seed, c, i, d)
+            z, u_acc, u_leaps = lr.draws(seed, c, i, d, "lmc")
             # all geometry from the state's position (the build's set_state departure does not show here: the
             # transcription never resets)
             _, _, G, dG = evalalldt(pars)

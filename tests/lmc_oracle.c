@@ -1,31 +1,19 @@
 /*
  * lmc_oracle.c -- CPU restatement of the two Lagrangian Monte Carlo samplers, ERMLMC (reference
  * src/samplers/ERMLMC.jl:84-179) and RMLMC (src/samplers/RMLMC.jl:89-179), on the probit / logistic models -- TEST
- * INFRASTRUCTURE ONLY.
+ * INFRASTRUCTURE ONLY.  A part of tests/manifold_oracle.c, after rmhmc_oracle.c.
  *
- * Includes tests/rmhmc_oracle.c unchanged (and through it pmala_oracle.c, smmala_oracle.c and oracle/oracle.c): the
- * log-target, gradient, tensor, Cholesky factor, inverse, solve, matvec, the weight's derivative, the d slabs of dG and
- * the two fused terms are theirs.  Added here, in the order mcmc.jl_amd/csrc/kernels/lmc.hip documents (DESIGN.md §4,
- * §5.12): the weighted Gram matrix K(v) = X' diag(w o X v) X (vxC(v) = 0.5 K(v) on these models), the factor of
- * G + c vxC, both samplers' steps with the tuner, set_state and the counters.
+ * The log-target, gradient, tensor, Cholesky factor, inverse, solve, matvec, the weight's derivative, the two fused
+ * terms, the state and the step loop (hmc_chain) are the earlier parts'.  Added here, in the order
+ * mcmc.jl_amd/csrc/kernels/lmc.hip documents: the weighted Gram matrix
+ * K(v) = X' diag(w o X v) X (vxC(v) = 0.5 K(v) on these models), the factor of G + c vxC and both samplers' proposal.
  *
  * Departures from the reference, as lmc.hip's header lists them: a trajectory that meets a log-target that is not
  * finite, a pivot <= 0 or not finite at any G, invG or G +- c vxC, or a position, velocity or ratio that is not finite
  * is rejected; a nRandomLeaps draw of 0 is rejected; set_state re-evaluates at the new position and the next step
  * recomputes all geometry from it.
  */
-#include "rmhmc_oracle.c"
-
-#define ORC_ERMLMC 10
-#define ORC_RMLMC 11
 #define ORC_TAG_LMC 6u
-
-typedef struct {
-    int64_t nrl_min, nrl_max;    /* smallest and largest nRandomLeaps drawn */
-    int64_t n_failed;            /* steps rejected for a failed trajectory */
-    int64_t n_zero;              /* steps whose nRandomLeaps draw was 0 */
-    int64_t n_adapt;             /* tuner adaptations */
-} lmc_counters;
 
 /* K = X' diag(w o t) X, t = X v by eta's chain: K[a][b], b <= a, the fma chain over the observations in ascending
    order from zero of fma(X[i][a], RN(RN(w_i t_i) X[i][b]), .) (the tensor's chain with another weight) */
@@ -153,123 +141,39 @@ static double lmc_leaps_uniform(uint64_t seed, uint32_t chain, uint32_t step) {
     return orc_uniform52(w[0], w[1]);
 }
 
-/* SamplerTask initialisation and the state after set_state: RMHMC's (x, lp, g and the tuner) */
-int64_t orc_lmc_init(const orc_model* m, const orc_sampler* s, int64_t C, rm_state* st) {
-    return orc_rm_init(m, s, C, st);
-}
-
-void orc_lmc_set_state(const orc_model* m, int64_t C, rm_state* st, const double* x) {
-    orc_rm_set_state(m, C, st, x);
-}
-
-static void lmc_chain(const orc_model* m, const orc_sampler* s, uint64_t seed, uint32_t chain, int64_t c, int64_t C,
-                      int64_t step0, int64_t burnin, int64_t thinning, int64_t len, int64_t tuner_burnin, rm_state* st,
-                      double* samples, double* grads, uint8_t* acc_out, lmc_counters* cn) {
+/* either sampler's proposal (ERMLMC.jl:100-160, RMLMC.jl:105-160): the velocity from chol(invG), the energy, the
+   leapfrogs with their deltaLogDet and E - E' + deltaLogDet */
+static int lmc_propose(const mf_run* r, uint32_t chain, uint32_t i, double eps, int64_t nl_fixed, const double* x,
+                       const double* g, double lp, double* xp, double* gp, double* lpp, int64_t* nrl, int* failed) {
+    const orc_model* m = r->m;
     const int d = m->d, nr = d * (d + 1) / 2;
-    const int semi = s->kind == ORC_RMLMC;
-    const int n_newton = semi ? (int)s->t0 : 0;
-    const int64_t max_leaps = s->max_leaps > 0 ? s->max_leaps : ((int64_t)1 << 20);
-    double x[SMM_MAXD], g[SMM_MAXD], xp[SMM_MAXD], v[SMM_MAXD], W[SMM_NR], z[SMM_MAXD + 4];
+    const int semi = r->s->kind == ORC_RMLMC;
+    const int n_newton = semi ? (int)r->s->t0 : 0;
+    double v[SMM_MAXD], W[SMM_NR], z[SMM_MAXD + 4];
     lmc_geo o;
-    smm_get(st->x, C, c, d, x);
-    smm_get(st->g, C, c, d, g);
-    double lp = st->lp[c];
-    double eps = s->tuner ? st->t_step[c] : s->leap_step;
-    int64_t nl_fixed = s->tuner ? (int64_t)st->t_leaps[c] : s->n_leaps;
-    int32_t n_acc = s->tuner ? st->t_acc[c] : 0, n_prop = s->tuner ? st->t_prop[c] : 0;
-    int64_t n_evals = 0;
-    for (int64_t t = 0; t < len; ++t) {
-        const int64_t i = step0 + t + 1;
-        if (s->tuner) n_prop += 1;
-        int failed = lmc_geom(m, x, &o);                 /* its log-target and gradient are the state's, bit for bit */
-        memcpy(W, o.iG, sizeof(double) * nr);
-        if (isnan(smm_chol(W, d))) failed = 1;                                /* chol(invG), ERMLMC.jl:103 */
-        orc_normals(seed, chain, (uint32_t)i, d, z);
-        rm_lmul(W, z, d, v);
-        const double E = lmc_energy(semi, lp, o.ld, o.G, v, d);
-        const int64_t nrl = (int64_t)ceil(lmc_leaps_uniform(seed, chain, (uint32_t)i) * (double)nl_fixed);
-        n_evals += nrl;
-        if (cn) {
-#ifdef _OPENMP
-#pragma omp critical(lmc_counters)
-#endif
-            {
-                if (nrl < cn->nrl_min) cn->nrl_min = nrl;
-                if (nrl > cn->nrl_max) cn->nrl_max = nrl;
-                if (nrl == 0) cn->n_zero += 1;
-            }
-        }
-        memcpy(xp, x, sizeof(double) * d);
-        double delta = 0.0;
-        for (int64_t l = 0; l < nrl && !failed; ++l)
-            failed = semi ? lmc_leap_s(m, n_newton, eps, xp, v, &o, &delta) : lmc_leap_e(m, eps, xp, v, &o, &delta);
-        int acc = 0;
-        if (!failed && nrl > 0) {
-            const double Ep = lmc_energy(semi, o.lp, o.ld, o.G, v, d);
-            const double ratio = (E - Ep) + delta;
-            if (isfinite(ratio)) acc = orc_mh_short_circuit(seed, chain, (uint32_t)i, ratio);
-            else failed = 1;
-        }
-        if (cn && failed) {
-#ifdef _OPENMP
-#pragma omp atomic
-#endif
-            cn->n_failed += 1;
-        }
-        if (acc) {
-            memcpy(x, xp, sizeof(double) * d);
-            memcpy(g, o.g, sizeof(double) * d);
-            lp = o.lp;
-            if (s->tuner) n_acc += 1;
-        }
-        int64_t kk;
-        if (orc_kept(i - step0, burnin, thinning, len, &kk)) {
-            if (samples)
-                for (int q = 0; q < d; ++q) samples[((size_t)kk * d + q) * C + c] = x[q];
-            if (grads)
-                for (int q = 0; q < d; ++q) grads[((size_t)kk * d + q) * C + c] = g[q];
-            if (acc_out) acc_out[(size_t)kk * C + c] = (uint8_t)acc;
-        }
-        if (s->tuner && i <= tuner_burnin && (i % s->adapt_step) == 0) {      /* ERMLMC.jl:170-176 (EmpiricalHMCTune) */
-            eps = eps * orc_tune_factor(n_acc, n_prop, s->target_rate);
-            double nlf = ceil(s->target_path / eps);
-            if (nlf > (double)s->max_step) nlf = (double)s->max_step;
-            if (nlf > (double)max_leaps) nlf = (double)max_leaps;
-            nl_fixed = (int64_t)nlf;
-            n_acc = 0;
-            n_prop = 0;
-            if (cn) {
-#ifdef _OPENMP
-#pragma omp atomic
-#endif
-                cn->n_adapt += 1;
-            }
-        }
-    }
-    smm_put(st->x, C, c, d, x);
-    smm_put(st->g, C, c, d, g);
-    st->lp[c] = lp;
-    if (s->tuner) {
-        st->t_step[c] = eps;
-        st->t_leaps[c] = (int32_t)nl_fixed;
-        st->t_acc[c] = n_acc;
-        st->t_prop[c] = n_prop;
-    }
-    if (st->n_evals) st->n_evals[c] += n_evals;
+    (void)g;
+    *failed = lmc_geom(m, x, &o);                        /* its log-target and gradient are the state's, bit for bit */
+    memcpy(W, o.iG, sizeof(double) * nr);
+    if (isnan(smm_chol(W, d))) *failed = 1;                                   /* chol(invG), ERMLMC.jl:103 */
+    orc_normals(r->seed, chain, i, d, z);
+    rm_lmul(W, z, d, v);
+    const double E = lmc_energy(semi, lp, o.ld, o.G, v, d);
+    *nrl = hmc_leap_count(r->cn, lmc_leaps_uniform(r->seed, chain, i), nl_fixed, 0.0);
+    memcpy(xp, x, sizeof(double) * d);
+    double delta = 0.0;
+    for (int64_t l = 0; l < *nrl && !*failed; ++l)
+        *failed = semi ? lmc_leap_s(m, n_newton, eps, xp, v, &o, &delta) : lmc_leap_e(m, eps, xp, v, &o, &delta);
+    if (*failed || *nrl <= 0) return 0;
+    const double Ep = lmc_energy(semi, o.lp, o.ld, o.G, v, d);
+    const double ratio = (E - Ep) + delta;
+    memcpy(gp, o.g, sizeof(double) * d);
+    *lpp = o.lp;
+    if (isfinite(ratio)) return orc_mh_short_circuit(r->seed, chain, i, ratio);
+    *failed = 1;
+    return 0;
 }
 
-/* run_serialmc of chains [c_begin, c_end) of a batch of C; outputs as orc_rm_run's; cn (may be NULL) is added to */
-void orc_lmc_run(const orc_model* m, const orc_sampler* s, uint64_t seed, int64_t chain0, int64_t C, int64_t c_begin,
-                 int64_t c_end, int64_t step0, int64_t burnin, int64_t thinning, int64_t len, int64_t tuner_burnin,
-                 rm_state* st, double* samples, double* grads, uint8_t* acc_out, lmc_counters* cn, int nthreads) {
-#ifdef _OPENMP
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
-#endif
-    for (int64_t c = c_begin; c < c_end; ++c)
-        lmc_chain(m, s, seed, (uint32_t)(chain0 + c), c, C, step0, burnin, thinning, len, tuner_burnin, st, samples,
-                  grads, acc_out, cn);
-    (void)nthreads;
-}
+static void lmc_chain(const mf_run* r, uint32_t chain, int64_t c) { hmc_chain(r, chain, c, lmc_propose); }
 
 /* the weighted Gram matrix of one point: x [d], v [d] -> packed K [nr] (vxC(v) = 0.5 K) and u2 = X' (w o (X v)^2)
    (vxC(v) v = 0.5 u2) */
@@ -298,14 +202,4 @@ double orc_lmc_leap(const orc_model* m, int semi, int n_newton, double h, double
     if (lmc_geom(m, x, &o)) return NAN;
     if (semi ? lmc_leap_s(m, n_newton, h, x, v, &o, &delta) : lmc_leap_e(m, h, x, v, &o, &delta)) return NAN;
     return delta;
-}
-
-/* the build's draws of (chain, step) for the literal transcription: normals z [d], the accept uniform and the leaps'
-   uniform */
-void orc_lmc_draws(uint64_t seed, uint32_t chain, uint32_t step, int d, double* z, double* u_acc, double* u_leaps) {
-    double zz[SMM_MAXD + 4];
-    orc_normals(seed, chain, step, d, zz);
-    for (int j = 0; j < d; ++j) z[j] = zz[j];
-    *u_acc = orc_accept_uniform(seed, chain, step);
-    *u_leaps = lmc_leaps_uniform(seed, chain, step);
 }

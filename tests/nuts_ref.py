@@ -1,62 +1,28 @@
 """ctypes harness for tests/nuts_oracle.c -- TEST INFRASTRUCTURE ONLY.
 
 The NUTS checker: tests/nuts_oracle.c includes oracle/oracle.c unchanged and adds the recursive restatement of
-NUTS.jl.  It is built with oracle/Makefile's CC and CFLAGS into tests/_build/ on first use, or when a source is newer
-than the library.  NutsChains is the checker's twin of an MCMCTask running NUTS, like oracle_ref.OracleChains.
+NUTS.jl.  It is built by checker_build.load.  NutsChains is the checker's twin of an MCMCTask running NUTS, like oracle_ref.OracleChains.
 """
 from __future__ import annotations
 
 import ctypes as ct
 import os
-import re
-import shlex
-import subprocess
 
 import numpy as np
 
+import checker_build
 import oracle_ref as orc
 from oracle_ref import D, OModel, OState, OracleModel, _d, _i
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "nuts_oracle.c")
-BUILD_DIR = os.path.join(HERE, "_build")
-LIB = os.path.join(BUILD_DIR, "libnuts_oracle.so")
 COUNTERS = ("outer_uturn", "inner_uturn", "leaf_fail", "maxdoublings", "zero_merges", "dir_plus", "dir_minus")
 
 _lib = None
 
 
-def _make_vars():
-    """CC and CFLAGS as oracle/Makefile sets them (CC ?= ..., so the environment's CC wins)"""
-    text = open(os.path.join(orc.ORACLE_DIR, "Makefile")).read()
-    cc = re.search(r"^CC\s*\?=\s*(.+)$", text, re.M).group(1).strip()
-    cflags = re.search(r"^CFLAGS\s*:=\s*(.+)$", text, re.M).group(1).strip()
-    return os.environ.get("CC", cc), shlex.split(cflags)
-
-
-def build() -> None:
-    cc, cflags = _make_vars()
-    os.makedirs(BUILD_DIR, exist_ok=True)
-    tmp = LIB + f".{os.getpid()}.tmp"
-    subprocess.run([cc, *cflags, "-shared", "-o", tmp, SRC, "-lm"], check=True, cwd=HERE)
-    os.replace(tmp, LIB)
-
-
-def _stale() -> bool:
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = [SRC] + [os.path.join(orc.ORACLE_DIR, f) for f in os.listdir(orc.ORACLE_DIR)
-                    if f.endswith((".c", ".h", ".inc"))]
-    return any(os.path.getmtime(p) > t for p in deps)
-
-
 def lib():
     global _lib
     if _lib is None:
-        if _stale():
-            build()
-        L = ct.CDLL(LIB)
+        L = checker_build.load("nuts_oracle.c", "libnuts_oracle.so")
         i64, P = ct.c_int64, ct.POINTER
         L.orc_nuts_init.restype = i64
         L.orc_nuts_init.argtypes = [P(OModel), ct.c_uint64, i64, i64, P(OState), D, ct.c_int]

@@ -1,16 +1,13 @@
 /*
  * pmala_oracle.c -- CPU restatement of the derivatives of the metric tensor of the probit / logistic models and of the
- * PMALA sampler (reference src/samplers/PMALA.jl:42-141) -- TEST INFRASTRUCTURE ONLY.
+ * SMMALA and PMALA samplers (reference src/samplers/SMMALA.jl:39-123, PMALA.jl:42-141) -- TEST INFRASTRUCTURE ONLY.
+ * A part of tests/manifold_oracle.c, after smmala_oracle.c.
  *
- * Includes tests/smmala_oracle.c unchanged (and through it oracle/oracle.c): the log-target, gradient, tensor, Cholesky
- * factor, inverse, matvec and quadratic form are SMMALA's.  Added here, in the order mcmc.jl_amd/csrc/kernels/pmala.hip
- * documents: the weight's derivative, the d slabs of dG, the fused drift correction
- * c = invG X' (w o qf) and the sampler's step.  dG is d slabs, each packed like G.
+ * The log-target, gradient, tensor, Cholesky factor, inverse, matvec and quadratic form are smmala_oracle.c's.  Added
+ * here, in the order mcmc.jl_amd/csrc/kernels/pmala.hip documents: the weight's derivative, the
+ * d slabs of dG, the fused drift correction c = invG X' (w o qf) and the pair's step, PMALA's with the correction and
+ * SMMALA's without (the kernels' smm_mala_step<CORR>).  dG is d slabs, each packed like G.
  */
-#include "smmala_oracle.c"
-
-#define ORC_PMALA 8
-
 typedef struct {
     double* x;        /* [d][C] */
     double* lp;       /* [C] */
@@ -18,7 +15,7 @@ typedef struct {
     double* G;        /* [d(d+1)/2][C] */
     double* invG;     /* [d(d+1)/2][C] */
     double* ft;       /* [d][C]  firstTerm = invG grad */
-    double* c;        /* [d][C]  sum(secondTerm, 2) */
+    double* c;        /* [d][C]  sum(secondTerm, 2); NULL for SMMALA */
     double* t_step;   /* [C] */
     int32_t* t_acc;
     int32_t* t_prop;
@@ -71,10 +68,31 @@ static void pm_dtensor(const orc_model* m, const double* x, double* dG) {
     }
 }
 
-/* the fused correction c = invG (X' (w o qf)), qf_o = x_o' invG x_o (pmala.hip's header):
+/* qf_o = x_o' invG x_o of observation row Xo (pmala.hip's header):
    M[j] = fma chain over (e, q') of fma(invG[j][4q' + e], X[o][4q' + e], .); P[j] = RN(M[j] X[o][j]);
-   s_q = ((P[q] + P[q+4]) + P[q+8]) + P[q+12]; qf = ((s_0 + s_1) + s_2) + s_3 from +0 (one MFMA with A = 1);
-   u[k] = fma chain over the observations of fma(X[o][k], RN(w_o qf_o), .); c = symv(invG, u) */
+   s_q = ((P[q] + P[q+4]) + P[q+8]) + P[q+12]; qf = ((s_0 + s_1) + s_2) + s_3 from +0 (one MFMA with A = 1) */
+static double pm_qform(const double* Xo, const double* iG, int d) {
+    double P[16];
+    for (int j = 0; j < 16; ++j) {
+        double M = 0.0;
+        for (int e = 0; e < 4; ++e)
+            for (int q = 0; q < 4; ++q) {
+                const int k = 4 * q + e;
+                const int ok = j < d && k < d;
+                M = fma(ok ? iG[smm_symi(j, k)] : 0.0, k < d ? Xo[k] : 0.0, M);
+            }
+        P[j] = M * (j < d ? Xo[j] : 0.0);
+    }
+    double qf = 0.0;
+    for (int q = 0; q < 4; ++q) {
+        const double s = ((P[q] + P[q + 4]) + P[q + 8]) + P[q + 12];
+        qf = fma(1.0, s, qf);
+    }
+    return qf;
+}
+
+/* the fused correction c = invG (X' (w o qf)): u[k] = fma chain over the observations of fma(X[o][k], RN(w_o qf_o), .);
+   c = symv(invG, u) */
 static void pm_corr(const orc_model* m, const double* x, const double* iG, double* c) {
     const int d = m->d;
     double u[SMM_MAXD];
@@ -82,23 +100,7 @@ static void pm_corr(const orc_model* m, const double* x, const double* iG, doubl
     for (int64_t o = 0; o < m->n; ++o) {
         const double* Xo = m->X + (size_t)o * d;
         const double w = pm_dw(m, pm_eta(Xo, x, d), m->Y[o]);
-        double P[16];
-        for (int j = 0; j < 16; ++j) {
-            double M = 0.0;
-            for (int e = 0; e < 4; ++e)
-                for (int q = 0; q < 4; ++q) {
-                    const int k = 4 * q + e;
-                    const int ok = j < d && k < d;
-                    M = fma(ok ? iG[smm_symi(j, k)] : 0.0, k < d ? Xo[k] : 0.0, M);
-                }
-            P[j] = M * (j < d ? Xo[j] : 0.0);
-        }
-        double qf = 0.0;
-        for (int q = 0; q < 4; ++q) {
-            const double s = ((P[q] + P[q + 4]) + P[q + 8]) + P[q + 12];
-            qf = fma(1.0, s, qf);
-        }
-        const double wq = w * qf;
+        const double wq = w * pm_qform(Xo, iG, d);
         for (int k = 0; k < d; ++k) u[k] = fma(Xo[k], wq, u[k]);
     }
     smm_symv(iG, u, d, c);
@@ -144,8 +146,8 @@ void orc_pm_corr(const orc_model* m, int64_t C, const double* xs, const double* 
     }
 }
 
-/* evaluation of chain c at st->x; derive: also invG, firstTerm and the correction.  Returns 1 for a start out of
-   support or a failed pivot. */
+/* evaluation of chain c at st->x; derive: also invG, firstTerm and (PMALA, st->c) the correction.  Returns 1 for a start
+   out of support or a failed pivot. */
 static int pm_eval_state(const orc_model* m, int64_t C, int64_t c, pm_state* st, int derive) {
     const int d = m->d, nr = d * (d + 1) / 2;
     double x[SMM_MAXD] = {0.0}, g[SMM_MAXD], Gc[SMM_NR], W[SMM_NR], iG[SMM_NR], ft[SMM_MAXD], cv[SMM_MAXD];
@@ -160,15 +162,17 @@ static int pm_eval_state(const orc_model* m, int64_t C, int64_t c, pm_state* st,
         if (isnan(smm_chol(W, d))) bad = 1;
         smm_inverse(W, d, iG);
         smm_symv(iG, g, d, ft);
-        pm_corr(m, x, iG, cv);
         smm_put(st->invG, C, c, nr, iG);
         smm_put(st->ft, C, c, d, ft);
-        smm_put(st->c, C, c, d, cv);
+        if (st->c) {
+            pm_corr(m, x, iG, cv);
+            smm_put(st->c, C, c, d, cv);
+        }
     }
     return bad;
 }
 
-/* SamplerTask initialisation (PMALA.jl:70-82) */
+/* SamplerTask initialisation (SMMALA.jl:62-70, PMALA.jl:70-82) */
 int64_t orc_pm_init(const orc_model* m, const orc_sampler* s, int64_t C, pm_state* st) {
     int64_t bad = 0;
     for (int64_t c = 0; c < C; ++c) {
@@ -183,7 +187,8 @@ int64_t orc_pm_init(const orc_model* m, const orc_sampler* s, int64_t C, pm_stat
     return bad;
 }
 
-/* the :reset hook as written (PMALA.jl:63-66): pars, logTarget, grad and G at x; invG, firstTerm and secondTerm stay */
+/* the :reset hook as written (SMMALA.jl:54-57, PMALA.jl:63-66): pars, logTarget, grad and G at x; invG, firstTerm and
+   secondTerm stay */
 void orc_pm_set_state(const orc_model* m, int64_t C, pm_state* st, const double* x) {
     for (int64_t c = 0; c < C; ++c) {
         for (int j = 0; j < m->d; ++j) st->x[(size_t)j * C + c] = x[(size_t)j * C + c];
@@ -192,9 +197,13 @@ void orc_pm_set_state(const orc_model* m, int64_t C, pm_state* st, const double*
     }
 }
 
-static void pm_chain(const orc_model* m, const orc_sampler* s, uint64_t seed, uint32_t chain, int64_t c, int64_t C,
-                     int64_t step0, int64_t burnin, int64_t thinning, int64_t len, int64_t tuner_burnin, pm_state* st,
-                     double* samples, double* grads, uint8_t* acc_out) {
+/* one chain of the pair; corr: PMALA's drift ft - c, else SMMALA's ft */
+static void mala_chain(const mf_run* r, uint32_t chain, int64_t c, int corr) {
+    const orc_model* m = r->m;
+    const orc_sampler* s = r->s;
+    pm_state* st = (pm_state*)r->st;
+    const uint64_t seed = r->seed;
+    const int64_t C = r->C;
     const int d = m->d, nr = d * (d + 1) / 2;
     double x[SMM_MAXD], g[SMM_MAXD], ft[SMM_MAXD], cv[SMM_MAXD], G[SMM_NR], iG[SMM_NR];
     double xp[SMM_MAXD], gp[SMM_MAXD], pft[SMM_MAXD], pc[SMM_MAXD], pG[SMM_NR], piG[SMM_NR], W[SMM_NR];
@@ -202,61 +211,57 @@ static void pm_chain(const orc_model* m, const orc_sampler* s, uint64_t seed, ui
     smm_get(st->x, C, c, d, x);
     smm_get(st->g, C, c, d, g);
     smm_get(st->ft, C, c, d, ft);
-    smm_get(st->c, C, c, d, cv);
+    if (corr) smm_get(st->c, C, c, d, cv);
     smm_get(st->G, C, c, nr, G);
     smm_get(st->invG, C, c, nr, iG);
     double lp = st->lp[c];
     double h = s->tuner ? st->t_step[c] : s->drift_step;
     int32_t n_acc = s->tuner ? st->t_acc[c] : 0, n_prop = s->tuner ? st->t_prop[c] : 0;
-    for (int64_t t = 0; t < len; ++t) {
-        const int64_t i = step0 + t + 1;
+    for (int64_t t = 0; t < r->len; ++t) {
+        const int64_t i = r->step0 + t + 1;
         if (s->tuner) n_prop += 1;
         const double half = h / 2.0;
         for (int k = 0; k < nr; ++k) W[k] = h * iG[k];
         const double ld1 = smm_chol(W, d);                                    /* U' = chol(h invG)' */
         int bad = isnan(ld1);
         orc_normals(seed, chain, (uint32_t)i, d, z);
-        for (int r = 0; r < d; ++r) {
+        for (int q = 0; q < d; ++q) {
             double u = 0.0;
-            for (int q = 0; q <= r; ++q) u = fma(W[smm_tri(r, q)], z[q], u);
-            const double pm = x[r] + half * (ft[r] - cv[r]);                  /* PMALA.jl:94 */
-            xp[r] = pm + u;                                                   /* PMALA.jl:98 */
-            ev[r] = pm - xp[r];
+            for (int k = 0; k <= q; ++k) u = fma(W[smm_tri(q, k)], z[k], u);
+            const double pm = x[q] + half * (corr ? ft[q] - cv[q]             /* PMALA.jl:94 */
+                                                  : ft[q]);                   /* SMMALA.jl:85 */
+            xp[q] = pm + u;                                                   /* SMMALA.jl:88, PMALA.jl:98 */
+            ev[q] = pm - xp[q];
         }
         const double qf = (-ld1) - 0.5 * smm_quad(G, ev, d, h);               /* probNewGivenOld */
-        const double lpp = smm_evalallt(m, xp, gp, pG);                       /* PMALA.jl:101 */
+        const double lpp = smm_evalallt(m, xp, gp, pG);                       /* SMMALA.jl:90, PMALA.jl:101 */
         const int oos = !isfinite(lpp);
         memcpy(W, pG, sizeof(double) * nr);
         if (isnan(smm_chol(W, d))) bad = 1;
-        smm_inverse(W, d, piG);                                               /* PMALA.jl:106 */
-        smm_symv(piG, gp, d, pft);                                            /* PMALA.jl:107 */
-        pm_corr(m, xp, piG, pc);                                              /* PMALA.jl:108-111 */
+        smm_inverse(W, d, piG);                                               /* SMMALA.jl:97, PMALA.jl:106 */
+        smm_symv(piG, gp, d, pft);                                            /* SMMALA.jl:98, PMALA.jl:107 */
+        if (corr) pm_corr(m, xp, piG, pc);                                    /* PMALA.jl:108-111 */
         for (int k = 0; k < nr; ++k) W[k] = h * piG[k];
         const double ld2 = smm_chol(W, d);
         if (isnan(ld2)) bad = 1;
-        for (int r = 0; r < d; ++r) ev[r] = (xp[r] + half * (pft[r] - pc[r])) - x[r];   /* PMALA.jl:114, 117 */
+        for (int q = 0; q < d; ++q)
+            ev[q] = (xp[q] + half * (corr ? pft[q] - pc[q]                    /* PMALA.jl:114, 117 */
+                                          : pft[q])) - x[q];                  /* SMMALA.jl:99-101 */
         const double qb = (-ld2) - 0.5 * smm_quad(pG, ev, d, h);              /* probOldGivenNew */
-        const double ratio = ((lpp + qb) - lp) - qf;                          /* PMALA.jl:119 */
+        const double ratio = ((lpp + qb) - lp) - qf;                          /* SMMALA.jl:104, PMALA.jl:119 */
         const int acc = !(bad || oos) && orc_mh_short_circuit(seed, chain, (uint32_t)i, ratio);
         if (acc) {
             memcpy(x, xp, sizeof(double) * d);
             memcpy(g, gp, sizeof(double) * d);
             memcpy(ft, pft, sizeof(double) * d);
-            memcpy(cv, pc, sizeof(double) * d);
+            if (corr) memcpy(cv, pc, sizeof(double) * d);
             memcpy(G, pG, sizeof(double) * nr);
             memcpy(iG, piG, sizeof(double) * nr);
             lp = lpp;
             if (s->tuner) n_acc += 1;
         }
-        int64_t kk;
-        if (orc_kept(i - step0, burnin, thinning, len, &kk)) {
-            if (samples)
-                for (int q = 0; q < d; ++q) samples[((size_t)kk * d + q) * C + c] = x[q];
-            if (grads)
-                for (int q = 0; q < d; ++q) grads[((size_t)kk * d + q) * C + c] = g[q];
-            if (acc_out) acc_out[(size_t)kk * C + c] = (uint8_t)acc;
-        }
-        if (s->tuner && i <= tuner_burnin && (i % s->adapt_step) == 0) {      /* PMALA.jl:131-137 */
+        mf_store_kept(r, i, c, x, g, acc);
+        if (s->tuner && i <= r->tuner_burnin && (i % s->adapt_step) == 0) {   /* SMMALA.jl:113-119, PMALA.jl:131-137 */
             h = h * orc_tune_factor(n_acc, n_prop, s->target_rate);
             n_acc = 0;
             n_prop = 0;
@@ -265,7 +270,7 @@ static void pm_chain(const orc_model* m, const orc_sampler* s, uint64_t seed, ui
     smm_put(st->x, C, c, d, x);
     smm_put(st->g, C, c, d, g);
     smm_put(st->ft, C, c, d, ft);
-    smm_put(st->c, C, c, d, cv);
+    if (corr) smm_put(st->c, C, c, d, cv);
     smm_put(st->G, C, c, nr, G);
     smm_put(st->invG, C, c, nr, iG);
     st->lp[c] = lp;
@@ -274,18 +279,8 @@ static void pm_chain(const orc_model* m, const orc_sampler* s, uint64_t seed, ui
         st->t_acc[c] = n_acc;
         st->t_prop[c] = n_prop;
     }
-    if (st->n_evals) st->n_evals[c] += len;
+    if (st->n_evals) st->n_evals[c] += r->len;
 }
 
-/* run_serialmc of chains [c_begin, c_end) of a batch of C; outputs as orc_smm_run's */
-void orc_pm_run(const orc_model* m, const orc_sampler* s, uint64_t seed, int64_t chain0, int64_t C, int64_t c_begin,
-                int64_t c_end, int64_t step0, int64_t burnin, int64_t thinning, int64_t len, int64_t tuner_burnin,
-                pm_state* st, double* samples, double* grads, uint8_t* acc_out, int nthreads) {
-#ifdef _OPENMP
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
-#endif
-    for (int64_t c = c_begin; c < c_end; ++c)
-        pm_chain(m, s, seed, (uint32_t)(chain0 + c), c, C, step0, burnin, thinning, len, tuner_burnin, st, samples,
-                 grads, acc_out);
-    (void)nthreads;
-}
+static void smm_chain(const mf_run* r, uint32_t chain, int64_t c) { mala_chain(r, chain, c, 0); }
+static void pm_chain(const mf_run* r, uint32_t chain, int64_t c) { mala_chain(r, chain, c, 1); }

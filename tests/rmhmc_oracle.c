@@ -1,16 +1,14 @@
 /*
  * rmhmc_oracle.c -- CPU restatement of the RMHMC sampler (reference src/samplers/RMHMC.jl:53-183) on the probit /
- * logistic models -- TEST INFRASTRUCTURE ONLY.
+ * logistic models, and of the frame the trajectory samplers share -- TEST INFRASTRUCTURE ONLY.
+ * A part of tests/manifold_oracle.c, after pmala_oracle.c.
  *
- * Includes tests/pmala_oracle.c unchanged (and through it smmala_oracle.c and oracle/oracle.c): the log-target,
- * gradient, tensor, Cholesky factor, inverse, matvec, the weight's derivative and the d slabs of dG are theirs.  Added
- * here, in the order mcmc.jl_amd/csrc/kernels/rmhmc.hip documents: the two fused tensor terms
- * X' (w o qf) and X' (w o t^2), the Cholesky solve, the momentum's quadratic form, and the sampler's step with its
- * counters.
+ * The log-target, gradient, tensor, Cholesky factor, inverse, matvec, the weight's derivative, the d slabs of dG and
+ * the per-observation quadratic form are the earlier parts'.  Added here, in the order
+ * mcmc.jl_amd/csrc/kernels/rmhmc.hip documents: the two fused tensor terms X' (w o qf) and
+ * X' (w o t^2), the Cholesky solve, the momentum's quadratic form; the state, the HMC-type tuner, the leap count, the
+ * counters and the step loop of RMHMC, ERMLMC and RMLMC; and RMHMC's proposal.
  */
-#include "pmala_oracle.c"
-
-#define ORC_RMHMC 9
 #define ORC_TAG_RMHMC 5u
 
 /* log 2 and log pi, the doubles nearest to them (RMHMC.jl:107 writes log(2) + d log(pi), not d log(2 pi)) */
@@ -28,15 +26,6 @@ typedef struct {
     int64_t* n_evals;
 } rm_state;
 
-/* what a run's steps covered, summed over the chains run */
-typedef struct {
-    int64_t n_plus, n_minus;     /* steps with timeStep = +1 / -1 */
-    int64_t nrl_min, nrl_max;    /* smallest and largest nRandomLeaps drawn */
-    int64_t n_failed;            /* steps rejected for out-of-support, a failed pivot or a non-finite position */
-    int64_t n_zero;              /* steps whose nRandomLeaps draw was 0 */
-    int64_t n_adapt;             /* tuner adaptations */
-} rm_counters;
-
 /* the fused terms at x with invG (either output may be NULL):
    u  = X' (w o qf), qf_o = x_o' invG x_o: pm_corr's chains; u[r] = trace(invG dG_r);
    u2 = X' (w o t^2), t = X v by eta's chain (k-slice e, row q <-> coordinate 4q + e): u2[r] = v' dG_r v; the weight is
@@ -51,23 +40,7 @@ static void rm_terms(const orc_model* m, const double* x, const double* iG, cons
         const double* Xo = m->X + (size_t)o * d;
         const double w = pm_dw(m, pm_eta(Xo, x, d), m->Y[o]);
         if (u) {
-            double P[16];
-            for (int j = 0; j < 16; ++j) {
-                double M = 0.0;
-                for (int e = 0; e < 4; ++e)
-                    for (int q = 0; q < 4; ++q) {
-                        const int k = 4 * q + e;
-                        const int ok = j < d && k < d;
-                        M = fma(ok ? iG[smm_symi(j, k)] : 0.0, k < d ? Xo[k] : 0.0, M);
-                    }
-                P[j] = M * (j < d ? Xo[j] : 0.0);
-            }
-            double qf = 0.0;
-            for (int q = 0; q < 4; ++q) {
-                const double s = ((P[q] + P[q + 4]) + P[q + 8]) + P[q + 12];
-                qf = fma(1.0, s, qf);
-            }
-            const double wq = w * qf;
+            const double wq = w * pm_qform(Xo, iG, d);
             for (int k = 0; k < d; ++k) u[k] = fma(Xo[k], wq, u[k]);
         }
         if (u2) {
@@ -172,8 +145,8 @@ static int rm_leap(const orc_model* m, int n_newton, double eh, double* xp, doub
     return 0;
 }
 
-/* SamplerTask initialisation (RMHMC.jl:82-86) */
-int64_t orc_rm_init(const orc_model* m, const orc_sampler* s, int64_t C, rm_state* st) {
+/* SamplerTask initialisation of the trajectory samplers (RMHMC.jl:82-86; ERMLMC's and RMLMC's state is the same) */
+int64_t orc_hmc_init(const orc_model* m, const orc_sampler* s, int64_t C, rm_state* st) {
     const int d = m->d;
     int64_t bad = 0;
     for (int64_t c = 0; c < C; ++c) {
@@ -193,8 +166,8 @@ int64_t orc_rm_init(const orc_model* m, const orc_sampler* s, int64_t C, rm_stat
     return bad;
 }
 
-/* the :reset hook (RMHMC.jl:74-77): pars, logTarget and grad at x; G and dG are recomputed by the next step */
-void orc_rm_set_state(const orc_model* m, int64_t C, rm_state* st, const double* x) {
+/* the :reset hook (RMHMC.jl:74-77): pars, logTarget and grad at x; the next step recomputes all geometry from it */
+void orc_hmc_set_state(const orc_model* m, int64_t C, rm_state* st, const double* x) {
     const int d = m->d;
     for (int64_t c = 0; c < C; ++c) {
         double xc[SMM_MAXD] = {0.0}, g[SMM_MAXD], G[SMM_NR];
@@ -206,124 +179,152 @@ void orc_rm_set_state(const orc_model* m, int64_t C, rm_state* st, const double*
     }
 }
 
-static void rm_chain(const orc_model* m, const orc_sampler* s, uint64_t seed, uint32_t chain, int64_t c, int64_t C,
-                     int64_t step0, int64_t burnin, int64_t thinning, int64_t len, int64_t tuner_burnin, rm_state* st,
-                     double* samples, double* grads, uint8_t* acc_out, rm_counters* cn) {
-    const int d = m->d, nr = d * (d + 1) / 2;
-    const int n_newton = (int)s->t0;
+/* the HMC-type tuner's state of one chain (EmpiricalHMCTune): the sampler's own values where it has no tuner */
+typedef struct {
+    double eps;
+    int64_t nl_fixed;
+    int32_t n_acc, n_prop;
+} hmc_tune;
+
+static void hmc_tune_load(const orc_sampler* s, const rm_state* st, int64_t c, hmc_tune* tn) {
+    tn->eps = s->tuner ? st->t_step[c] : s->leap_step;
+    tn->nl_fixed = s->tuner ? (int64_t)st->t_leaps[c] : s->n_leaps;
+    tn->n_acc = s->tuner ? st->t_acc[c] : 0;
+    tn->n_prop = s->tuner ? st->t_prop[c] : 0;
+}
+
+/* RMHMC.jl:174-180, ERMLMC.jl:170-176 */
+static void hmc_tune_adapt(const orc_sampler* s, hmc_tune* tn, mf_counters* cn) {
     const int64_t max_leaps = s->max_leaps > 0 ? s->max_leaps : ((int64_t)1 << 20);
-    double x[SMM_MAXD], g[SMM_MAXD], xp[SMM_MAXD], gp[SMM_MAXD], mom[SMM_MAXD], v[SMM_MAXD], tr[SMM_MAXD];
-    double G[SMM_NR], W[SMM_NR], iG[SMM_NR], g0[SMM_MAXD], z[SMM_MAXD + 4];
-    smm_get(st->x, C, c, d, x);
-    smm_get(st->g, C, c, d, g);
-    double lp = st->lp[c];
-    double eps = s->tuner ? st->t_step[c] : s->leap_step;
-    int64_t nl_fixed = s->tuner ? (int64_t)st->t_leaps[c] : s->n_leaps;
-    int32_t n_acc = s->tuner ? st->t_acc[c] : 0, n_prop = s->tuner ? st->t_prop[c] : 0;
-    int64_t n_evals = 0;
-    for (int64_t t = 0; t < len; ++t) {
-        const int64_t i = step0 + t + 1;
-        if (s->tuner) n_prop += 1;
-        (void)smm_evalallt(m, x, g0, G);                                      /* RMHMC.jl:100 */
-        memcpy(W, G, sizeof(double) * nr);
-        const double ld0 = smm_chol(W, d);                                    /* RMHMC.jl:102 */
-        int failed = isnan(ld0);
-        smm_inverse(W, d, iG);                                                /* RMHMC.jl:101 */
-        orc_normals(seed, chain, (uint32_t)i, d, z);
-        rm_lmul(W, z, d, mom);                                                /* RMHMC.jl:105 */
-        smm_symv(iG, mom, d, v);
-        const double H = rm_hamiltonian(lp, ld0, rm_dot(mom, v, d), d);       /* RMHMC.jl:107 */
-        rm_terms(m, x, iG, NULL, tr, NULL);                                   /* RMHMC.jl:110-114 */
-        double u, nz;
-        rm_draws(seed, chain, (uint32_t)i, &u, &nz);
-        const double ts = nz > 0.5 ? 1.0 : -1.0;                              /* RMHMC.jl:117 */
-        const int64_t nrl = (int64_t)ceil(u * (double)nl_fixed);              /* RMHMC.jl:118 */
-        const double eh = ts * (eps / 2.0);
-        n_evals += nrl;
-        if (cn) {
-#ifdef _OPENMP
-#pragma omp critical(rm_counters)
-#endif
-            {
-                if (ts > 0.0) cn->n_plus += 1; else cn->n_minus += 1;
-                if (nrl < cn->nrl_min) cn->nrl_min = nrl;
-                if (nrl > cn->nrl_max) cn->nrl_max = nrl;
-                if (nrl == 0) cn->n_zero += 1;
-            }
-        }
-        memcpy(xp, x, sizeof(double) * d);
-        memcpy(gp, g, sizeof(double) * d);
-        double lpp = lp, ldp = ld0;
-        for (int64_t l = 0; l < nrl && !failed; ++l)
-            failed = rm_leap(m, n_newton, eh, xp, mom, gp, iG, tr, &lpp, &ldp);
-        int acc = 0;
-        if (!failed && nrl > 0) {
-            smm_symv(iG, mom, d, v);
-            const double Hp = rm_hamiltonian(lpp, ldp, rm_dot(mom, v, d), d);  /* RMHMC.jl:161-162 */
-            const double ratio = H - Hp;                                      /* RMHMC.jl:164 */
-            if (isfinite(ratio)) acc = orc_mh_short_circuit(seed, chain, (uint32_t)i, ratio);
-            else failed = 1;
-        }
-        if (cn && failed) {
+    tn->eps = tn->eps * orc_tune_factor(tn->n_acc, tn->n_prop, s->target_rate);
+    double nlf = ceil(s->target_path / tn->eps);
+    if (nlf > (double)s->max_step) nlf = (double)s->max_step;
+    if (nlf > (double)max_leaps) nlf = (double)max_leaps;
+    tn->nl_fixed = (int64_t)nlf;
+    tn->n_acc = 0;
+    tn->n_prop = 0;
+    if (cn) {
 #ifdef _OPENMP
 #pragma omp atomic
 #endif
-            cn->n_failed += 1;
+        cn->n_adapt += 1;
+    }
+}
+
+static void hmc_tune_store(const orc_sampler* s, rm_state* st, int64_t c, const hmc_tune* tn) {
+    if (!s->tuner) return;
+    st->t_step[c] = tn->eps;
+    st->t_leaps[c] = (int32_t)tn->nl_fixed;
+    st->t_acc[c] = tn->n_acc;
+    st->t_prop[c] = tn->n_prop;
+}
+
+/* nRandomLeaps = ceil(u nLeaps) (RMHMC.jl:118) and what the counters keep of it; ts: the step's timeStep, 0 for a
+   sampler that draws none */
+static int64_t hmc_leap_count(mf_counters* cn, double u, int64_t nl_fixed, double ts) {
+    const int64_t nrl = (int64_t)ceil(u * (double)nl_fixed);
+    if (cn) {
+#ifdef _OPENMP
+#pragma omp critical(mf_counters)
+#endif
+        {
+            if (ts > 0.0) cn->n_plus += 1;
+            if (ts < 0.0) cn->n_minus += 1;
+            if (nrl < cn->nrl_min) cn->nrl_min = nrl;
+            if (nrl > cn->nrl_max) cn->nrl_max = nrl;
+            if (nrl == 0) cn->n_zero += 1;
+        }
+    }
+    return nrl;
+}
+
+/* a sampler's proposal of step i from (x, g, lp) with leapStep eps and nLeaps nl_fixed: the end of its trajectory in
+   (xp, gp, *lpp), the leaps it drew in *nrl, whether the trajectory failed in *failed; returns the accept decision */
+typedef int (*hmc_propose_fn)(const mf_run* r, uint32_t chain, uint32_t i, double eps, int64_t nl_fixed,
+                              const double* x, const double* g, double lp, double* xp, double* gp, double* lpp,
+                              int64_t* nrl, int* failed);
+
+/* one chain of a trajectory sampler: everything but the proposal */
+static void hmc_chain(const mf_run* r, uint32_t chain, int64_t c, hmc_propose_fn propose) {
+    const orc_sampler* s = r->s;
+    rm_state* st = (rm_state*)r->st;
+    const int64_t C = r->C;
+    const int d = r->m->d;
+    double x[SMM_MAXD], g[SMM_MAXD], xp[SMM_MAXD], gp[SMM_MAXD];
+    smm_get(st->x, C, c, d, x);
+    smm_get(st->g, C, c, d, g);
+    double lp = st->lp[c];
+    hmc_tune tn;
+    hmc_tune_load(s, st, c, &tn);
+    int64_t n_evals = 0;
+    for (int64_t t = 0; t < r->len; ++t) {
+        const int64_t i = r->step0 + t + 1;
+        if (s->tuner) tn.n_prop += 1;
+        double lpp = lp;
+        int64_t nrl = 0;
+        int failed = 0;
+        const int acc = propose(r, chain, (uint32_t)i, tn.eps, tn.nl_fixed, x, g, lp, xp, gp, &lpp, &nrl, &failed);
+        n_evals += nrl;
+        if (r->cn && failed) {
+#ifdef _OPENMP
+#pragma omp atomic
+#endif
+            r->cn->n_failed += 1;
         }
         if (acc) {
             memcpy(x, xp, sizeof(double) * d);
             memcpy(g, gp, sizeof(double) * d);
             lp = lpp;
-            if (s->tuner) n_acc += 1;
+            if (s->tuner) tn.n_acc += 1;
         }
-        int64_t kk;
-        if (orc_kept(i - step0, burnin, thinning, len, &kk)) {
-            if (samples)
-                for (int q = 0; q < d; ++q) samples[((size_t)kk * d + q) * C + c] = x[q];
-            if (grads)
-                for (int q = 0; q < d; ++q) grads[((size_t)kk * d + q) * C + c] = g[q];
-            if (acc_out) acc_out[(size_t)kk * C + c] = (uint8_t)acc;
-        }
-        if (s->tuner && i <= tuner_burnin && (i % s->adapt_step) == 0) {      /* RMHMC.jl:174-180 (EmpiricalHMCTune) */
-            eps = eps * orc_tune_factor(n_acc, n_prop, s->target_rate);
-            double nlf = ceil(s->target_path / eps);
-            if (nlf > (double)s->max_step) nlf = (double)s->max_step;
-            if (nlf > (double)max_leaps) nlf = (double)max_leaps;
-            nl_fixed = (int64_t)nlf;
-            n_acc = 0;
-            n_prop = 0;
-            if (cn) {
-#ifdef _OPENMP
-#pragma omp atomic
-#endif
-                cn->n_adapt += 1;
-            }
-        }
+        mf_store_kept(r, i, c, x, g, acc);
+        if (s->tuner && i <= r->tuner_burnin && (i % s->adapt_step) == 0) hmc_tune_adapt(s, &tn, r->cn);
     }
     smm_put(st->x, C, c, d, x);
     smm_put(st->g, C, c, d, g);
     st->lp[c] = lp;
-    if (s->tuner) {
-        st->t_step[c] = eps;
-        st->t_leaps[c] = (int32_t)nl_fixed;
-        st->t_acc[c] = n_acc;
-        st->t_prop[c] = n_prop;
-    }
+    hmc_tune_store(s, st, c, &tn);
     if (st->n_evals) st->n_evals[c] += n_evals;
 }
 
-/* run_serialmc of chains [c_begin, c_end) of a batch of C; outputs as orc_smm_run's; cn (may be NULL) is added to */
-void orc_rm_run(const orc_model* m, const orc_sampler* s, uint64_t seed, int64_t chain0, int64_t C, int64_t c_begin,
-                int64_t c_end, int64_t step0, int64_t burnin, int64_t thinning, int64_t len, int64_t tuner_burnin,
-                rm_state* st, double* samples, double* grads, uint8_t* acc_out, rm_counters* cn, int nthreads) {
-#ifdef _OPENMP
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
-#endif
-    for (int64_t c = c_begin; c < c_end; ++c)
-        rm_chain(m, s, seed, (uint32_t)(chain0 + c), c, C, step0, burnin, thinning, len, tuner_burnin, st, samples,
-                 grads, acc_out, cn);
-    (void)nthreads;
+/* RMHMC's proposal (RMHMC.jl:100-164): the momentum from chol(G), the Hamiltonian, timeStep, the generalised
+   leapfrogs and H - H' */
+static int rm_propose(const mf_run* r, uint32_t chain, uint32_t i, double eps, int64_t nl_fixed, const double* x,
+                      const double* g, double lp, double* xp, double* gp, double* lpp, int64_t* nrl, int* failed) {
+    const orc_model* m = r->m;
+    const int d = m->d, nr = d * (d + 1) / 2;
+    const int n_newton = (int)r->s->t0;
+    double mom[SMM_MAXD], v[SMM_MAXD], tr[SMM_MAXD], G[SMM_NR], W[SMM_NR], iG[SMM_NR], g0[SMM_MAXD], z[SMM_MAXD + 4];
+    (void)smm_evalallt(m, x, g0, G);                                          /* RMHMC.jl:100 */
+    memcpy(W, G, sizeof(double) * nr);
+    const double ld0 = smm_chol(W, d);                                        /* RMHMC.jl:102 */
+    *failed = isnan(ld0);
+    smm_inverse(W, d, iG);                                                    /* RMHMC.jl:101 */
+    orc_normals(r->seed, chain, i, d, z);
+    rm_lmul(W, z, d, mom);                                                    /* RMHMC.jl:105 */
+    smm_symv(iG, mom, d, v);
+    const double H = rm_hamiltonian(lp, ld0, rm_dot(mom, v, d), d);           /* RMHMC.jl:107 */
+    rm_terms(m, x, iG, NULL, tr, NULL);                                       /* RMHMC.jl:110-114 */
+    double u, nz;
+    rm_draws(r->seed, chain, i, &u, &nz);
+    const double ts = nz > 0.5 ? 1.0 : -1.0;                                  /* RMHMC.jl:117 */
+    *nrl = hmc_leap_count(r->cn, u, nl_fixed, ts);                            /* RMHMC.jl:118 */
+    const double eh = ts * (eps / 2.0);
+    memcpy(xp, x, sizeof(double) * d);
+    memcpy(gp, g, sizeof(double) * d);
+    double ldp = ld0;
+    for (int64_t l = 0; l < *nrl && !*failed; ++l)
+        *failed = rm_leap(m, n_newton, eh, xp, mom, gp, iG, tr, lpp, &ldp);
+    if (*failed || *nrl <= 0) return 0;
+    smm_symv(iG, mom, d, v);
+    const double Hp = rm_hamiltonian(*lpp, ldp, rm_dot(mom, v, d), d);        /* RMHMC.jl:161-162 */
+    const double ratio = H - Hp;                                              /* RMHMC.jl:164 */
+    if (isfinite(ratio)) return orc_mh_short_circuit(r->seed, chain, i, ratio);
+    *failed = 1;
+    return 0;
 }
+
+static void rm_chain(const mf_run* r, uint32_t chain, int64_t c) { hmc_chain(r, chain, c, rm_propose); }
 
 /* the fused terms of one point: x [d], packed invG [nr], v [d] -> u = X' (w o qf), u2 = X' (w o (X v)^2) */
 void orc_rm_terms(const orc_model* m, const double* x, const double* iG, const double* v, double* u, double* u2) {
@@ -337,17 +338,6 @@ int orc_rm_solve(int d, const double* G, const double* b, double* out) {
     if (isnan(smm_chol(W, d))) return 0;
     rm_solve(W, b, d, out);
     return 1;
-}
-
-/* the build's draws of (chain, step) for the literal transcription: normals z [d], the accept uniform, the leaps'
-   uniform and the sign's normal */
-void orc_rm_draws(uint64_t seed, uint32_t chain, uint32_t step, int d, double* z, double* u_acc, double* u_leaps,
-                  double* nz) {
-    double zz[SMM_MAXD + 4];
-    orc_normals(seed, chain, step, d, zz);
-    for (int j = 0; j < d; ++j) z[j] = zz[j];
-    *u_acc = orc_accept_uniform(seed, chain, step);
-    rm_draws(seed, chain, step, u_leaps, nz);
 }
 
 /* the trajectory's energy error for the integrator check: from x [d] with momentum mom [d], nl generalised leapfrogs

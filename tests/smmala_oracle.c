@@ -1,31 +1,15 @@
 /*
- * smmala_oracle.c -- CPU restatement of the metric tensor of the probit / logistic models and of the SMMALA sampler
- * (reference src/samplers/SMMALA.jl:39-123) -- TEST INFRASTRUCTURE ONLY.
+ * smmala_oracle.c -- CPU restatement of the metric tensor of the probit / logistic models -- TEST INFRASTRUCTURE ONLY.
+ * A part of tests/manifold_oracle.c, which includes oracle/oracle.c before it.
  *
- * Includes oracle/oracle.c unchanged: the log-target and the gradient come from orc_eval, the normals and the accept
- * uniform from orc_normals / orc_mh_short_circuit.  Added here, in the order the kernels document
+ * The log-target and the gradient come from orc_eval.  Added here, in the order the kernels document
  * (mcmc.jl_amd/csrc/kernels/smmala.hip): the tensor, the Cholesky factor, the inverse from the
- * factor, the matvecs and quadratic forms, and the sampler's step.  Matrices are packed lower rows, element (r, c),
- * c <= r, at [r(r+1)/2 + c], chain-strided like the RAM factor.
+ * factor, the matvecs and quadratic forms.  Matrices are packed lower rows, element (r, c), c <= r, at
+ * [r(r+1)/2 + c], chain-strided like the RAM factor.  The sampler's step (reference src/samplers/SMMALA.jl:39-123) is
+ * pmala_oracle.c's driver without the correction term.
  */
-#include "../oracle/oracle.c"
-
-#define ORC_SMMALA 7
 #define SMM_MAXD 16
 #define SMM_NR (SMM_MAXD * (SMM_MAXD + 1) / 2)
-
-typedef struct {
-    double* x;        /* [d][C] */
-    double* lp;       /* [C] */
-    double* g;        /* [d][C] */
-    double* G;        /* [d(d+1)/2][C] */
-    double* invG;     /* [d(d+1)/2][C] */
-    double* ft;       /* [d][C]  firstTerm = invG grad */
-    double* t_step;   /* [C] */
-    int32_t* t_acc;
-    int32_t* t_prop;
-    int64_t* n_evals;
-} smm_state;
 
 static int smm_tri(int r, int c) { return r * (r + 1) / 2 + c; }
 static int smm_symi(int r, int c) { return r >= c ? smm_tri(r, c) : smm_tri(c, r); }
@@ -142,153 +126,4 @@ void orc_smm_evalallt(const orc_model* m, int64_t C, const double* xs, double* l
         if (grad) smm_put(grad, C, c, d, g);
         smm_put(G, C, c, nr, Gc);
     }
-}
-
-/* evaluation of chain c at st->x; derive: also invG and firstTerm.  Returns 1 for a start out of support or a failed
-   pivot. */
-static int smm_eval_state(const orc_model* m, int64_t C, int64_t c, smm_state* st, int derive) {
-    const int d = m->d, nr = d * (d + 1) / 2;
-    double x[SMM_MAXD] = {0.0}, g[SMM_MAXD], Gc[SMM_NR], W[SMM_NR], iG[SMM_NR], ft[SMM_MAXD];
-    smm_get(st->x, C, c, d, x);
-    const double lp = smm_evalallt(m, x, g, Gc);
-    st->lp[c] = lp;
-    smm_put(st->g, C, c, d, g);
-    smm_put(st->G, C, c, nr, Gc);
-    int bad = !isfinite(lp);
-    if (derive) {
-        memcpy(W, Gc, sizeof(double) * nr);
-        if (isnan(smm_chol(W, d))) bad = 1;
-        smm_inverse(W, d, iG);
-        smm_symv(iG, g, d, ft);
-        smm_put(st->invG, C, c, nr, iG);
-        smm_put(st->ft, C, c, d, ft);
-    }
-    return bad;
-}
-
-/* SamplerTask initialisation (SMMALA.jl:62-70) */
-int64_t orc_smm_init(const orc_model* m, const orc_sampler* s, int64_t C, smm_state* st) {
-    int64_t bad = 0;
-    for (int64_t c = 0; c < C; ++c) {
-        bad += smm_eval_state(m, C, c, st, 1);
-        if (s->tuner) {
-            st->t_step[c] = s->drift_step;
-            st->t_acc[c] = 0;
-            st->t_prop[c] = 0;
-        }
-        if (st->n_evals) st->n_evals[c] = 1;
-    }
-    return bad;
-}
-
-/* the :reset hook as written (SMMALA.jl:54-57): pars, logTarget, grad and G at x; invG and firstTerm stay */
-void orc_smm_set_state(const orc_model* m, int64_t C, smm_state* st, const double* x) {
-    for (int64_t c = 0; c < C; ++c) {
-        for (int j = 0; j < m->d; ++j) st->x[(size_t)j * C + c] = x[(size_t)j * C + c];
-        (void)smm_eval_state(m, C, c, st, 0);
-        if (st->n_evals) st->n_evals[c] += 1;
-    }
-}
-
-static void smm_chain(const orc_model* m, const orc_sampler* s, uint64_t seed, uint32_t chain, int64_t c, int64_t C,
-                      int64_t step0, int64_t burnin, int64_t thinning, int64_t len, int64_t tuner_burnin,
-                      smm_state* st, double* samples, double* grads, uint8_t* acc_out) {
-    const int d = m->d, nr = d * (d + 1) / 2;
-    double x[SMM_MAXD], g[SMM_MAXD], ft[SMM_MAXD], G[SMM_NR], iG[SMM_NR];
-    double xp[SMM_MAXD], gp[SMM_MAXD], pft[SMM_MAXD], pG[SMM_NR], piG[SMM_NR], W[SMM_NR];
-    double z[SMM_MAXD + 4], ev[SMM_MAXD];
-    smm_get(st->x, C, c, d, x);
-    smm_get(st->g, C, c, d, g);
-    smm_get(st->ft, C, c, d, ft);
-    smm_get(st->G, C, c, nr, G);
-    smm_get(st->invG, C, c, nr, iG);
-    double lp = st->lp[c];
-    double h = s->tuner ? st->t_step[c] : s->drift_step;
-    int32_t n_acc = s->tuner ? st->t_acc[c] : 0, n_prop = s->tuner ? st->t_prop[c] : 0;
-    for (int64_t t = 0; t < len; ++t) {
-        const int64_t i = step0 + t + 1;
-        if (s->tuner) n_prop += 1;
-        const double half = h / 2.0;
-        for (int k = 0; k < nr; ++k) W[k] = h * iG[k];
-        const double ld1 = smm_chol(W, d);                                    /* U' = chol(h invG)' */
-        int bad = isnan(ld1);
-        orc_normals(seed, chain, (uint32_t)i, d, z);
-        for (int r = 0; r < d; ++r) {
-            double u = 0.0;
-            for (int q = 0; q <= r; ++q) u = fma(W[smm_tri(r, q)], z[q], u);
-            const double pm = x[r] + half * ft[r];                            /* SMMALA.jl:85 */
-            xp[r] = pm + u;                                                   /* SMMALA.jl:88 */
-            ev[r] = pm - xp[r];
-        }
-        const double qf = (-ld1) - 0.5 * smm_quad(G, ev, d, h);               /* probNewGivenOld */
-        const double lpp = smm_evalallt(m, xp, gp, pG);                       /* SMMALA.jl:90 */
-        const int oos = !isfinite(lpp);
-        memcpy(W, pG, sizeof(double) * nr);
-        if (isnan(smm_chol(W, d))) bad = 1;
-        smm_inverse(W, d, piG);                                               /* SMMALA.jl:97 */
-        smm_symv(piG, gp, d, pft);                                            /* SMMALA.jl:98 */
-        for (int k = 0; k < nr; ++k) W[k] = h * piG[k];
-        const double ld2 = smm_chol(W, d);
-        if (isnan(ld2)) bad = 1;
-        for (int r = 0; r < d; ++r) ev[r] = (xp[r] + half * pft[r]) - x[r];   /* SMMALA.jl:99-101 */
-        const double qb = (-ld2) - 0.5 * smm_quad(pG, ev, d, h);              /* probOldGivenNew */
-        const double ratio = ((lpp + qb) - lp) - qf;                          /* SMMALA.jl:104 */
-        const int acc = !(bad || oos) && orc_mh_short_circuit(seed, chain, (uint32_t)i, ratio);
-        if (acc) {
-            memcpy(x, xp, sizeof(double) * d);
-            memcpy(g, gp, sizeof(double) * d);
-            memcpy(ft, pft, sizeof(double) * d);
-            memcpy(G, pG, sizeof(double) * nr);
-            memcpy(iG, piG, sizeof(double) * nr);
-            lp = lpp;
-            if (s->tuner) n_acc += 1;
-        }
-        int64_t kk;
-        if (orc_kept(i - step0, burnin, thinning, len, &kk)) {
-            if (samples)
-                for (int q = 0; q < d; ++q) samples[((size_t)kk * d + q) * C + c] = x[q];
-            if (grads)
-                for (int q = 0; q < d; ++q) grads[((size_t)kk * d + q) * C + c] = g[q];
-            if (acc_out) acc_out[(size_t)kk * C + c] = (uint8_t)acc;
-        }
-        if (s->tuner && i <= tuner_burnin && (i % s->adapt_step) == 0) {      /* SMMALA.jl:113-119 */
-            h = h * orc_tune_factor(n_acc, n_prop, s->target_rate);
-            n_acc = 0;
-            n_prop = 0;
-        }
-    }
-    smm_put(st->x, C, c, d, x);
-    smm_put(st->g, C, c, d, g);
-    smm_put(st->ft, C, c, d, ft);
-    smm_put(st->G, C, c, nr, G);
-    smm_put(st->invG, C, c, nr, iG);
-    st->lp[c] = lp;
-    if (s->tuner) {
-        st->t_step[c] = h;
-        st->t_acc[c] = n_acc;
-        st->t_prop[c] = n_prop;
-    }
-    if (st->n_evals) st->n_evals[c] += len;
-}
-
-/* run_serialmc of chains [c_begin, c_end) of a batch of C; outputs as orc_run's.  tuner_burnin: the burnin the tuner
-   sees (the sampler's global step counter against it) */
-void orc_smm_run(const orc_model* m, const orc_sampler* s, uint64_t seed, int64_t chain0, int64_t C, int64_t c_begin,
-                 int64_t c_end, int64_t step0, int64_t burnin, int64_t thinning, int64_t len, int64_t tuner_burnin,
-                 smm_state* st, double* samples, double* grads, uint8_t* acc_out, int nthreads) {
-#ifdef _OPENMP
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads > 0 ? nthreads : 1)
-#endif
-    for (int64_t c = c_begin; c < c_end; ++c)
-        smm_chain(m, s, seed, (uint32_t)(chain0 + c), c, C, step0, burnin, thinning, len, tuner_burnin, st, samples,
-                  grads, acc_out);
-    (void)nthreads;
-}
-
-/* the build's normals and accept uniform, for the literal numpy transcription of SMMALA.jl */
-void orc_smm_draws(uint64_t seed, uint32_t chain, uint32_t step, int d, double* z, double* u) {
-    double zz[SMM_MAXD + 4];
-    orc_normals(seed, chain, step, d, zz);
-    for (int j = 0; j < d; ++j) z[j] = zz[j];
-    *u = orc_accept_uniform(seed, chain, step);
 }

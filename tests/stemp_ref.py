@@ -8,46 +8,20 @@ and step counters it advances, so that a second call continues them as a second 
 from __future__ import annotations
 
 import ctypes as ct
-import os
-import subprocess
 
 import numpy as np
 
-import oracle_ref as orc
-from nuts_ref import _make_vars
+import checker_build
 from oracle_ref import D, OModel, OSampler, OState, _d
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "stemp_oracle.c")
-BUILD_DIR = os.path.join(HERE, "_build")
-LIB = os.path.join(BUILD_DIR, "libstemp_oracle.so")
 
 _lib = None
-
-
-def build() -> None:
-    cc, cflags = _make_vars()
-    os.makedirs(BUILD_DIR, exist_ok=True)
-    tmp = LIB + f".{os.getpid()}.tmp"
-    subprocess.run([cc, *cflags, "-shared", "-o", tmp, SRC, "-lm"], check=True, cwd=HERE)
-    os.replace(tmp, LIB)
-
-
-def _stale() -> bool:
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = [SRC] + [os.path.join(orc.ORACLE_DIR, f) for f in os.listdir(orc.ORACLE_DIR)
-                    if f.endswith((".c", ".h", ".inc"))]
-    return any(os.path.getmtime(p) > t for p in deps)
 
 
 def lib():
     global _lib
     if _lib is None:
-        if _stale():
-            build()
-        L = ct.CDLL(LIB)
+        L = checker_build.load("stemp_oracle.c", "libstemp_oracle.so")
         i64, P, V = ct.c_int64, ct.POINTER, ct.c_void_p
         L.orc_serialtempmc.restype = None
         L.orc_serialtempmc.argtypes = [V, V, V, i64, V, V, V, ct.c_int, i64, i64, i64, i64, D, ct.c_uint64, D,

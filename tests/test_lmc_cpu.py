@@ -11,11 +11,11 @@ import numpy as np
 import pytest
 
 import lmc_cases as lc
-import lmc_ref as lr
+import manifold_harness as mh
+import manifold_ref as lr
 import mcmchip as mc
 import pmala_cases as pc
 import smmala_cases as sc
-import smmala_ref as sr
 from mcmchip import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -117,23 +117,15 @@ def test_validation_and_t0_round_trip():
 def test_python_refusals(cls):
     """gradient, tensor, dtensor, in that order, without a device"""
     nm = cls.__name__
-    t = sc.model("probit_vaso").target
-    r = mc.SerialMC(steps=10)
-    with pytest.raises(AssertionError, match=nm + " sampler requires model with function of tensor derivatives"):
-        sc.model("probit_vaso") * cls() * r
-    with pytest.raises(AssertionError, match=nm + " sampler requires model with tensor function"):
-        sc.model("probit_vaso", False) * cls() * r
-    with pytest.raises(AssertionError, match=nm + " sampler requires model with gradient function"):
-        mc.model(t, vars=np.zeros(3)) * cls() * r
-    pc.model("probit_vaso") * cls(0.5, TUNER) * r
+    mh.python_refusals(nm, cls)
+    pc.model("probit_vaso") * cls(0.5, TUNER) * mc.SerialMC(steps=10)
     from mcmchip import api
     assert nm in api.__all__ and getattr(mc, nm) is cls
 
 
 def test_texts_name_the_new_samplers():
     header = open(os.path.join(ROOT, "include", "mcmc_hip.h")).read()
-    hook = open(os.path.join(ROOT, "mcmc.jl_amd", "julia", "mcmc_jl_hook.jl")).read()
-    mod = open(os.path.join(ROOT, "mcmc.jl_amd", "julia", "MCMCHip.jl")).read()
+    hook, mod = mh.julia_texts()
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     readme = open(os.path.join(ROOT, "README.md")).read()
     integ = open(os.path.join(ROOT, "INTEGRATION.md")).read()
@@ -145,14 +137,6 @@ def test_texts_name_the_new_samplers():
     assert "ermlmc(" in mod and "rmlmc(" in mod
     assert "### 5.12" in design and "TAG_LMC" in design and "lmc_step" in design
     assert "ERMLMC" in readme and "RMLMC" in readme and "ERMLMC" in integ and "RMLMC" in integ
-
-
-def _slabs(dGp, c, d):
-    """dG [d, d, d] of point c from the checker's packed slabs, slab r at [:, :, r]"""
-    out = np.empty((d, d, d))
-    for r in range(d):
-        out[:, :, r] = lr.unpack(dGp[r, :, c:c + 1], d)[:, :, 0]
-    return out
 
 
 @pytest.mark.parametrize("kind", ["logistic", "logistic_neg", "probit"])
@@ -172,7 +156,7 @@ def test_symmetry_identity(kind, d):
     worst = 0.0
     for c in range(6):
         v = rng.standard_normal(d)
-        dG = _slabs(dGp, c, d)
+        dG = mh.slabs(dGp, c, d)
         Cl = lc.literal_C(dG)
         vxC = lc.literal_vxC(v, Cl)
         got, gotv = lr.gram(m, x[:, c], v)
@@ -211,12 +195,6 @@ def test_logdet_and_solve(d):
     assert any(np.linalg.eigvalsh(G + c * vxC).min() < 0 for c in (big, -big))
 
 
-def _run_all(oc, r):
-    """every step of a run with a burnin, kept: the tuner sees r.burnin, the kept range is the whole run"""
-    oc.tuner_burnin = r.burnin
-    return oc.run(mc.SerialMC(steps=r.len, burnin=0), nthreads=1)
-
-
 # leapStep 0.2 and seed 3: chosen on the CPU so that the transcription itself meets no failed trajectory (at 0.3 the
 # tuned RMLMC run on probit_vaso grows its step until G + h vxC has a negative determinant), no draw of 0 and no accept
 # test nearer a tie than the bound below
@@ -232,7 +210,7 @@ def test_checker_against_literal_transcription(which, tuned, seed, kind):
     sp = mc.ERMLMC(6, 0.2, tn) if kind == "ermlmc" else mc.RMLMC(6, 0.2, 4, tn)
     r = mc.SerialMC(steps=20, burnin=15)
     oc = lr.LmcChains(m, sp, 8, seed=seed)
-    s, g, a = oc.run(mc.SerialMC(steps=20, burnin=0), nthreads=1) if not tuned else _run_all(oc, r)
+    s, g, a = oc.run(mc.SerialMC(steps=20, burnin=0), nthreads=1) if not tuned else mh.run_all(oc, r)
     ls, lg, la, margin = lc.literal(m, sp, 8, 20, seed, 15)
     scale = np.abs(ls).max()
     gscale = np.abs(lg).max()
@@ -300,10 +278,7 @@ def test_checker_ermlmc_posterior_agrees_with_smmala():
     r = mc.SerialMC(steps=200, burnin=100)
     m = pc.logistic_40_10()
     a, _, acc = lr.LmcChains(m, mc.ERMLMC(3, 0.5), C, seed=21).run(r)
-    b, _, _ = sr.SmmalaChains(sc.logistic_40_10(), mc.SMMALA(0.5), C, seed=22).run(r)
-    ca, cb = a.mean(axis=0), b.mean(axis=0)
-    ma, mb = ca.mean(axis=1), cb.mean(axis=1)
-    se = np.sqrt(ca.var(axis=1, ddof=1) / C + cb.var(axis=1, ddof=1) / C)
-    z = np.abs(ma - mb) / se
+    b, _, _ = lr.SmmalaChains(sc.logistic_40_10(), mc.SMMALA(0.5), C, seed=22).run(r)
+    z, ma, mb, se = mh.posterior_z(a, b, C)
     print("z", z, "acceptance", acc.mean())
     assert (z < 5).all(), (ma, mb, se)

@@ -8,14 +8,15 @@ import re
 import numpy as np
 import pytest
 
+import manifold_harness as mh
+import manifold_ref as pr
 import mcmchip as mc
 import pmala_cases as pc
-import pmala_ref as pr
 import smmala_cases as sc
-import smmala_ref as sr
 from mcmchip import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sr = pr          # the tensor is the same checker's
 
 
 def test_validation_and_symbols():
@@ -51,13 +52,7 @@ def test_python_refusals():
     with pytest.raises(AssertionError, match="needs its tensor function"):
         mc.model(t, vars=np.zeros(3), gradient=True, dtensor=True)
     r = mc.SerialMC(steps=10)
-    with pytest.raises(AssertionError, match="PMALA sampler requires model with function of tensor derivatives"):
-        sc.model("probit_vaso") * mc.PMALA(1.0) * r
-    with pytest.raises(AssertionError, match="PMALA sampler requires model with tensor function"):
-        sc.model("probit_vaso", False) * mc.PMALA(1.0) * r
-    nograd = mc.model(t, vars=np.zeros(3))
-    with pytest.raises(AssertionError, match="PMALA sampler requires model with gradient function"):
-        nograd * mc.PMALA(1.0) * r
+    mh.python_refusals("PMALA", lambda: mc.PMALA(1.0))
     pc.model("probit_vaso") * mc.PMALA(1.0) * r                     # spins without a device
     pc.model("probit_vaso") * mc.SMMALA(1.0) * r                    # a dtensor model serves SMMALA too
 
@@ -95,7 +90,7 @@ def test_checker_dG_probit_literal(name):
     _, _, _, dGp = pr.evalalldt(m, x)
     for c in range(C):
         ref = pc.closed_dG(m, x[:, c])
-        got = np.stack([pr.unpack(dGp[i, :, c:c + 1], d)[:, :, 0] for i in range(d)], axis=2)
+        got = mh.slabs(dGp, c, d)
         assert np.abs(got - ref).max() <= 1e-10 * np.abs(ref).max(), (name, c)
 
 
@@ -193,8 +188,7 @@ def test_checker_against_literal_transcription(which, h, seed):
 
 
 def test_julia_hook_text():
-    hook = open(os.path.join(ROOT, "mcmc.jl_amd", "julia", "mcmc_jl_hook.jl")).read()
-    mod = open(os.path.join(ROOT, "mcmc.jl_amd", "julia", "MCMCHip.jl")).read()
+    hook, mod = mh.julia_texts()
     assert re.search(r"hip_sampler\(s::PMALA\) = hip_cfg\(8, 0\., s\.driftStep", hook)
     assert re.search(r"isa\(s, PMALA\)", hook) and re.search(r"const PMALA_K = 8\b", mod)
     assert re.search(r"hasdtensor", hook)

@@ -9,15 +9,16 @@ import re
 import numpy as np
 import pytest
 
+import manifold_harness as mh
+import manifold_ref as rr
 import mcmchip as mc
 import pmala_cases as pc
-import rmhmc_ref as rr
 import smmala_cases as sc
-import smmala_ref as sr
 from mcmchip import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TUNER = mc.EmpiricalMCMCTuner(0.8)
+sr = rr          # the tensor is the same checker's
 
 
 def test_constructor_forms():
@@ -78,21 +79,13 @@ def test_validation_and_t0_round_trip():
 
 
 def test_python_refusals():
-    t = sc.model("probit_vaso").target
-    r = mc.SerialMC(steps=10)
-    with pytest.raises(AssertionError, match="RMHMC sampler requires model with function of tensor derivatives"):
-        sc.model("probit_vaso") * mc.RMHMC() * r
-    with pytest.raises(AssertionError, match="RMHMC sampler requires model with tensor function"):
-        sc.model("probit_vaso", False) * mc.RMHMC() * r
-    with pytest.raises(AssertionError, match="RMHMC sampler requires model with gradient function"):
-        mc.model(t, vars=np.zeros(3)) * mc.RMHMC() * r
-    pc.model("probit_vaso") * mc.RMHMC(0.5, TUNER) * r                 # the example's line spins without a device
+    mh.python_refusals("RMHMC", mc.RMHMC)
+    pc.model("probit_vaso") * mc.RMHMC(0.5, TUNER) * mc.SerialMC(steps=10)                 # the example's line spins without a device
 
 
 def test_texts_name_the_new_limits():
     header = open(os.path.join(ROOT, "include", "mcmc_hip.h")).read()
-    hook = open(os.path.join(ROOT, "mcmc.jl_amd", "julia", "mcmc_jl_hook.jl")).read()
-    mod = open(os.path.join(ROOT, "mcmc.jl_amd", "julia", "MCMCHip.jl")).read()
+    hook, mod = mh.julia_texts()
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     readme = open(os.path.join(ROOT, "README.md")).read()
     integ = open(os.path.join(ROOT, "INTEGRATION.md")).read()
@@ -102,10 +95,6 @@ def test_texts_name_the_new_limits():
     assert re.search(r"const RMHMC_K = 9\b", mod) and "rmhmc(" in mod
     assert "### 5.11" in design and "TAG_RMHMC" in design and "rm_step" in design
     assert "RMHMC" in readme and "RMHMC(0.5, EmpMCTuner(0.8" in integ
-
-
-def _slabs(dGp, c, d):
-    return [rr.unpack(dGp[i, :, c:c + 1], d)[:, :, 0] for i in range(d)]
 
 
 @pytest.mark.parametrize("kind", ["logistic", "probit"])
@@ -128,9 +117,9 @@ def test_fused_terms_against_literal(kind, d):
         iG = invG[:, :, c]
         v = iG @ p
         u, u2 = rr.terms(m, x[:, c], iGp[:, c], v)
-        dG = _slabs(dGp, c, d)
-        tr = np.array([np.trace(iG @ dG[r]) for r in range(d)])
-        mt = np.array([0.5 * (p @ (iG @ dG[r]) @ (iG @ p)) for r in range(d)])
+        dG = mh.slabs(dGp, c, d)
+        tr = np.array([np.trace(iG @ dG[:, :, r]) for r in range(d)])
+        mt = np.array([0.5 * (p @ (iG @ dG[:, :, r]) @ (iG @ p)) for r in range(d)])
         for got, lit in ((u, tr), (0.5 * u2, mt)):
             scale = np.abs(lit).max()
             dev = np.abs(got - lit).max()
@@ -178,7 +167,7 @@ def _literal(m, sp, C, steps, seed, burnin):
                 nLeaps, leapStep = t_nLeaps, t_leapStep
             else:
                 nLeaps, leapStep = sp.nLeaps, sp.leapStep
-            z, u_acc, u_leaps, nz = rr.draws(seed, c, i, d)
+            z, u_acc, u_leaps, nz = rr.draws(seed, c, i, d, "rmhmc")
             proposedPars = pars.copy()
             G = pc.closed_G(m, proposedPars)
             invG = np.linalg.inv(G)
@@ -251,7 +240,7 @@ def test_checker_against_literal_transcription(which, tuned, seed):
     sp = mc.RMHMC(6, 0.5, 4, tn)                                      # the reference's defaults (RMHMC.jl:42)
     r = mc.SerialMC(steps=20, burnin=15)
     oc = rr.RmhmcChains(m, sp, 8, seed=seed)
-    s, g, a = oc.run(mc.SerialMC(steps=20, burnin=0), nthreads=1) if not tuned else _run_all(oc, r)
+    s, g, a = oc.run(mc.SerialMC(steps=20, burnin=0), nthreads=1) if not tuned else mh.run_all(oc, r)
     ls, lg, la, margin = _literal(m, sp, 8, 20, seed, 15)
     scale = np.abs(ls).max()
     gscale = np.abs(lg).max()
@@ -264,12 +253,6 @@ def test_checker_against_literal_transcription(which, tuned, seed):
     assert np.array_equal(a.astype(bool), la)
     assert la.any()
     assert dev <= 1e-10
-
-
-def _run_all(oc, r):
-    """every step of a run with a burnin, kept: the tuner sees r.burnin, the kept range is the whole run"""
-    oc.tuner_burnin = r.burnin
-    return oc.run(mc.SerialMC(steps=r.len, burnin=0), nthreads=1)
 
 
 def test_generalised_leapfrog_is_second_order():
@@ -296,9 +279,6 @@ def test_checker_posterior_agrees_with_smmala():
     m = pc.logistic_40_10()
     a, _, acc = rr.RmhmcChains(m, mc.RMHMC(3, 0.5, 4), C, seed=21).run(r)
     b, _, _ = sr.SmmalaChains(sc.logistic_40_10(), mc.SMMALA(0.5), C, seed=22).run(r)
-    ca, cb = a.mean(axis=0), b.mean(axis=0)
-    ma, mb = ca.mean(axis=1), cb.mean(axis=1)
-    se = np.sqrt(ca.var(axis=1, ddof=1) / C + cb.var(axis=1, ddof=1) / C)
-    z = np.abs(ma - mb) / se
+    z, ma, mb, se = mh.posterior_z(a, b, C)
     print("z", z, "acceptance", acc.mean())
     assert (z < 5).all(), (ma, mb, se)

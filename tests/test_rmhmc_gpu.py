@@ -1,24 +1,17 @@
-"""RMHMC (rmhmc.hip) against the checker (tests/rmhmc_oracle.c), bit for bit."""
-import ctypes as ct
-import functools
-
+"""RMHMC (rmhmc.hip) against the checker (tests/manifold_oracle.c), bit for bit."""
 import numpy as np
 import pytest
 
+import manifold_harness as mh
+import manifold_ref as rr
 import mcmchip as mc
 import pmala_cases as pc
-import rmhmc_ref as rr
-import smmala_cases as sc
+from manifold_harness import R40, _create, _raises, bits
 from mcmchip import _lib
 
 pytestmark = pytest.mark.gpu
-R40 = mc.SerialMC(steps=40, burnin=10, thinning=3)
 # (nLeaps, leapStep, nNewton): one leapfrog with one pass, and five with four; the step at d = 16 is smaller
 SAMPLERS = {"l1n1": (1, 0.8, 1), "l5n4": (5, 0.6, 4)}
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def sampler(key, name):
@@ -26,41 +19,18 @@ def sampler(key, name):
     return mc.RMHMC(n, e / 2 if pc.SHAPES[name][2] == 16 else e, k)
 
 
-@functools.lru_cache(maxsize=None)
-def reference(name, key):
-    """the checker's R40 run of a shape, computed once and shared: (samples, grads, accept, final state, evals,
-    counters)"""
-    C = pc.SHAPES[name][3]
-    oc = rr.RmhmcChains(pc.model(name), sampler(key, name), C, seed=1)
-    s, g, a = oc.run(R40)
-    state = {k: getattr(oc, k).copy() for k in ("x", "lp", "g")}
-    for v in (s, g, a, *state.values()):
-        v.setflags(write=False)
-    return s, g, a, state, oc.evals, oc.counters
-
-
-def state_of(oc):
-    return {k: getattr(oc, k) for k in ("x", "lp", "g")}
-
-
-def assert_same(ch, task, s, g, a, state, evals, what=""):
-    assert np.isfinite(s).all() and np.isfinite(g).all(), what + ": the checker's chains carry a NaN"
-    assert np.array_equal(bits(ch._samples), bits(s)), what + ": samples"
-    assert np.array_equal(bits(ch._gradients), bits(g)), what + ": gradients"
-    assert np.array_equal(ch.diagnostics["accept"].T, a.astype(bool)), what + ": accept bits"
-    assert np.array_equal(bits(ch.final_x), bits(state["x"])), what + ": final_x"
-    assert np.array_equal(bits(ch.final_lp), bits(state["lp"])), what + ": final_lp"
-    assert task.evals == evals, what + ": evals"
+FAM = mh.Family(rr.RmhmcChains, pc, lambda name, key: sampler(key, name))
 
 
 @pytest.mark.parametrize("key", list(SAMPLERS))
 @pytest.mark.parametrize("name", list(pc.SHAPES))
 def test_parity(gpu, name, key):
     C = pc.SHAPES[name][3]
-    s, g, a, state, evals, cn = reference(name, key)
+    ref = FAM.reference(name, key)
+    a, cn = ref.a, ref.counters
     t = (pc.model(name) * sampler(key, name) * R40).batch(C, seed=1)
     ch = mc.run(t)
-    assert_same(ch, t, s, g, a, state, evals, name)
+    FAM.assert_same(ch, t, ref, name)
     assert t.step_kernel == "rm_step"
     assert a.any(), (name, a.mean())
     ts = t.tuner_state()
@@ -76,21 +46,16 @@ def test_parity(gpu, name, key):
 @pytest.mark.parametrize("spl", [0, 1, 7])
 def test_steps_per_launch(gpu, spl):
     name = "logistic_n17_d5"
-    s, g, a, state, evals, _ = reference(name, "l5n4")
     t = (pc.model(name) * sampler("l5n4", name) * R40).batch(70, seed=1, steps_per_launch=spl)
-    assert_same(mc.run(t), t, s, g, a, state, evals, f"spl {spl}")
+    FAM.assert_same(mc.run(t), t, FAM.reference(name, "l5n4"), f"spl {spl}")
 
 
 def test_chain_offset(gpu):
     """chains 32.. of the 70 as a batch of their own (global ids by chain_offset): a workgroup's trajectory length is
     its own chains' maximum, and a chain's arithmetic does not depend on it"""
     name = "logistic_n17_d5"
-    s, g, a, _, _, _ = reference(name, "l5n4")
     t = (pc.model(name) * sampler("l5n4", name) * R40).batch(38, seed=1, chain_offset=32)
-    ch = mc.run(t)
-    assert np.array_equal(bits(ch._samples), bits(s[:, :, 32:]))
-    assert np.array_equal(bits(ch._gradients), bits(g[:, :, 32:]))
-    assert np.array_equal(ch.diagnostics["accept"].T, a[:, 32:].astype(bool))
+    mh.assert_outputs(mc.run(t), FAM.reference(name, "l5n4"), chains=slice(32, None))
 
 
 def test_tuned(gpu):
@@ -100,9 +65,9 @@ def test_tuned(gpu):
     r = mc.SerialMC(steps=40, burnin=20)
     oc = rr.RmhmcChains(pc.model(name), sp, 70, seed=2)
     t = (pc.model(name) * sp * r).batch(70, seed=2)
-    s, g, a = oc.run(r)
+    ref = FAM.ran(oc, r)
     assert oc.counters.n_adapt == 4 * 70
-    assert_same(mc.run(t), t, s, g, a, state_of(oc), oc.evals, "tuned")
+    FAM.assert_same(mc.run(t), t, ref, "tuned")
     ts = t.tuner_state()
     assert np.array_equal(bits(ts["step"]), bits(oc.t_step))
     assert np.array_equal(ts["nleaps"], oc.t_leaps)
@@ -111,49 +76,15 @@ def test_tuned(gpu):
 
 
 def test_fork_reset_set_state(gpu):
+    """set_state: pars, logTarget and grad at x; the next step recomputes the rest"""
     name = "logistic_n17_d5"
-    m = pc.model(name)
-    sp = sampler("l5n4", name)
-    r = mc.SerialMC(steps=20)
-    oc = rr.RmhmcChains(m, sp, 70, seed=5)
-    t = (m * sp * r).batch(70, seed=5)
-    s, g, a = oc.run(r)
-    assert_same(mc.run(t), t, s, g, a, state_of(oc), oc.evals, "first run")
-    # fork chains [16, 48): continues exactly those chains
-    h = ct.c_void_p()
-    _lib.check(_lib.load().mcmc_chains_fork(t.handle(), 16, 32, ct.byref(h)))
-    try:
-        samples = np.empty((20, 5, 32))
-        out = _lib.Outputs()
-        out.samples = samples.ctypes.data
-        rc = _lib.RunnerCfg(0, 1, 20)
-        _lib.check(_lib.load().mcmc_run_serialmc(h, ct.byref(rc), ct.byref(out)))
-    finally:
-        _lib.load().mcmc_chains_destroy(h)
-    s2, g2, a2 = oc.run(r)
-    assert np.array_equal(bits(samples), bits(s2[:, :, 16:48])), "fork"
-    assert_same(mc.run(t), t, s2, g2, a2, state_of(oc), oc.evals, "source after fork")
-    # set_state: pars, logTarget and grad at x; the next step recomputes the rest
-    x = np.random.default_rng(9).standard_normal((5, 70)) * 0.3
-    lp = mc.reset(t, x)
-    assert np.array_equal(bits(lp), bits(oc.set_state(x)))
-    s3, g3, a3 = oc.run(r)
-    assert_same(mc.run(t), t, s3, g3, a3, state_of(oc), oc.evals, "after set_state")
-    t.reset()
-    oc.reset()
-    s4, g4, a4 = oc.run(r)
-    assert_same(mc.run(t), t, s4, g4, a4, state_of(oc), oc.evals, "after reset")
-    assert np.array_equal(bits(s4), bits(s))
+    mh.fork_reset_set_state(FAM, pc.model(name), sampler("l5n4", name))
 
 
 def test_group_equals_one_context(gpu):
     name = "logistic_neg_n33_d16"
-    s, g, a, _, _, _ = reference(name, "l5n4")
     t = (pc.model(name) * sampler("l5n4", name) * R40).batch(100, seed=1, devices=(0, 0))
-    ch = mc.run(t)
-    assert np.array_equal(bits(ch._samples), bits(s))
-    assert np.array_equal(bits(ch._gradients), bits(g))
-    assert np.array_equal(ch.diagnostics["accept"].T, a.astype(bool))
+    mh.assert_outputs(mc.run(t), FAM.reference(name, "l5n4"))
 
 
 def test_failed_trajectories_are_rejected(gpu):
@@ -163,41 +94,16 @@ def test_failed_trajectories_are_rejected(gpu):
     sp = mc.RMHMC(5, 1.2, 2)
     oc = rr.RmhmcChains(pc.model(name), sp, 70, seed=3)
     t = (pc.model(name) * sp * R40).batch(70, seed=3)
-    s, g, a = oc.run(R40)
-    assert oc.counters.n_failed > 0 and a.any(), (oc.counters.n_failed, a.mean())
-    assert_same(mc.run(t), t, s, g, a, state_of(oc), oc.evals, "failed trajectories")
-
-
-def _raises(code, text, f):
-    with pytest.raises(_lib.MCMCError) as e:
-        f()
-    assert e.value.code == code and text in str(e.value), (e.value.code, str(e.value))
-
-
-def _create(m, cfg, C=4):
-    h = ct.c_void_p()
-    try:
-        _lib.check(_lib.load().mcmc_chains_create(m._handle(0), ct.byref(cfg), C, 0, ct.c_uint64(1), None, ct.byref(h)))
-    finally:
-        if h.value:
-            _lib.load().mcmc_chains_destroy(h)
+    ref = FAM.ran(oc, R40)
+    assert oc.counters.n_failed > 0 and ref.a.any(), (oc.counters.n_failed, ref.a.mean())
+    FAM.assert_same(mc.run(t), t, ref, "failed trajectories")
 
 
 def test_refusals(gpu):
     cfg = mc.RMHMC().cfg()
-    # d > 16
-    X, Y = sc.data(20, 17, 1)
-    wide = mc.model(mc.LogisticRegression(X, Y), vars=np.zeros(17), gradient=True, tensor=True, dtensor=True)
-    _raises(_lib.MCMC_E_UNSUPPORTED, "RMHMC is built for d <= 16", lambda: _create(wide, cfg))
-    # a model without tensor derivatives, after the gradient and tensor checks
+    # d > 16; a model without tensor derivatives, after the gradient and tensor checks
+    mh.gradient_refusals("RMHMC", cfg, "RMHMC is built for d <= 16")
     name = "logistic_n17_d5"
-    _raises(_lib.MCMC_E_NEEDS_GRADIENT, "RMHMC sampler requires model with function of tensor derivatives",
-            lambda: _create(sc.model(name), cfg))
-    _raises(_lib.MCMC_E_NEEDS_GRADIENT, "RMHMC sampler requires model with tensor function",
-            lambda: _create(sc.model(name, False), cfg))
-    nograd = mc.model(sc.model(name).target, vars=np.zeros(5))
-    _raises(_lib.MCMC_E_NEEDS_GRADIENT, "RMHMC sampler requires model with gradient function",
-            lambda: _create(nograd, cfg))
     # nNewton travels in t0: an integer in 1 .. 2^31 - 1
     for t0 in (2.5, 2.0 ** 31):
         bad = mc.RMHMC().cfg()
@@ -205,21 +111,8 @@ def test_refusals(gpu):
         _raises(_lib.MCMC_E_INVALID_ARG, "t0 carries nNewton", lambda: _create(pc.model(name), bad))
     # storeLeaps and SeqMC
     t = (pc.model(name) * mc.RMHMC() * R40).batch(8, seed=1)
-    buf = np.zeros(8 * 5 * 8)
-    nl = np.zeros(8, dtype=np.int32)
-    rc = _lib.load().mcmc_chains_store_leaps(t.handle(), 1, _lib.dptr(buf), _lib.dptr(buf), _lib.dptr(buf),
-                                             _lib.dptr(buf), _lib.dptr(buf), nl.ctypes.data)
-    assert rc == _lib.MCMC_E_UNSUPPORTED and b"RMHMC" in _lib.load().mcmc_last_error()
-    targets = (ct.c_void_p * 1)(t.handle())
-    cfgq = (ct.c_int64 * 2)(2, 0)
-    trig = ct.c_double(0.1)
-    sbuf = (ct.c_char * 24)()
-    ct.memmove(sbuf, cfgq, 16)
-    ct.memmove(ct.addressof(sbuf) + 16, ct.addressof(trig), 8)
-    parts = np.zeros((5, 8))
-    rc = _lib.load().mcmc_run_seqmc(targets, 1, 8, parts.ctypes.data, ct.addressof(sbuf), ct.c_uint64(1), 0, None, None,
-                                    None, None)
-    assert rc == _lib.MCMC_E_UNSUPPORTED and b"RMHMC" in _lib.load().mcmc_last_error()
+    mh.store_leaps_refuses(t, "RMHMC")
+    mh.seqmc_refuses(t, "RMHMC")
 
 
 def test_posterior_agrees_with_smmala(gpu):
@@ -232,10 +125,7 @@ def test_posterior_agrees_with_smmala(gpu):
     m = pc.logistic_40_10()
     a = mc.run((m * mc.RMHMC(3, 0.5, 4) * r).batch(C, seed=21))
     b = mc.run((m * mc.SMMALA(0.5) * r).batch(C, seed=22))
-    ca, cb = a._samples.mean(axis=0), b._samples.mean(axis=0)          # chain means [d][C]
-    ma, mb = ca.mean(axis=1), cb.mean(axis=1)
-    se = np.sqrt(ca.var(axis=1, ddof=1) / C + cb.var(axis=1, ddof=1) / C)
-    z = np.abs(ma - mb) / se
+    z, ma, mb, se = mh.posterior_z(a._samples, b._samples, C)
     print("means", ma, mb, "se", se, "z", z, "acceptance", a.diagnostics["accept"].mean(),
           b.diagnostics["accept"].mean())
     assert (z < 5).all(), (ma, mb, se)

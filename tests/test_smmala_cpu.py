@@ -7,9 +7,10 @@ import re
 import numpy as np
 import pytest
 
+import manifold_harness as mh
+import manifold_ref as sr
 import mcmchip as mc
 import smmala_cases as sc
-import smmala_ref as sr
 from mcmchip import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,13 +43,8 @@ def test_python_refusals():
     assert mc.SMMALA(scale=0.3).driftStep == 0.3
     tuned = mc.SMMALA(mc.EmpiricalMCMCTuner(0.6))
     assert tuned.driftStep == 1.0 and tuned.cfg().tuner == 1
-    r = mc.SerialMC(steps=10)
-    with pytest.raises(AssertionError, match="SMMALA sampler requires model with tensor function"):
-        sc.model("probit_vaso", False) * mc.SMMALA(1.0) * r
-    nograd = mc.model(sc.model("probit_vaso").target, vars=np.zeros(3))
-    with pytest.raises(AssertionError, match="SMMALA sampler requires model with gradient function"):
-        nograd * mc.SMMALA(1.0) * r
-    sc.model("probit_vaso") * mc.SMMALA(1.0) * r                  # spins without a device
+    mh.python_refusals("SMMALA", lambda: mc.SMMALA(1.0), dtensor=False)
+    sc.model("probit_vaso") * mc.SMMALA(1.0) * mc.SerialMC(steps=10)      # spins without a device
 
 
 def _closed_form(m, x):
@@ -134,7 +130,6 @@ def test_checker_against_literal_transcription(which, h):
 
 
 def test_julia_hook_text():
-    hook = open(os.path.join(ROOT, "mcmc.jl_amd", "julia", "mcmc_jl_hook.jl")).read()
-    mod = open(os.path.join(ROOT, "mcmc.jl_amd", "julia", "MCMCHip.jl")).read()
+    hook, mod = mh.julia_texts()
     assert re.search(r"hip_sampler\(s::SMMALA\) = hip_cfg\(7, 0\., s\.driftStep", hook)
     assert re.search(r"isa\(s, SMMALA\)", hook) and re.search(r"const SMMALA_K = 7\b", mod)

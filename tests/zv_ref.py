@@ -6,45 +6,19 @@ oracle/Makefile's CC and CFLAGS into tests/_build/ on first use, or when its sou
 from __future__ import annotations
 
 import ctypes as ct
-import os
-import re
-import shlex
-import subprocess
 
 import numpy as np
 
-import oracle_ref as orc
+import checker_build
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "zv_oracle.c")
-BUILD_DIR = os.path.join(HERE, "_build")
-LIB = os.path.join(BUILD_DIR, "libzv_oracle.so")
 
 _lib = None
-
-
-def _make_vars():
-    """CC and CFLAGS as oracle/Makefile sets them (CC ?= ..., so the environment's CC wins)"""
-    text = open(os.path.join(orc.ORACLE_DIR, "Makefile")).read()
-    cc = re.search(r"^CC\s*\?=\s*(.+)$", text, re.M).group(1).strip()
-    cflags = re.search(r"^CFLAGS\s*:=\s*(.+)$", text, re.M).group(1).strip()
-    return os.environ.get("CC", cc), shlex.split(cflags)
-
-
-def build() -> None:
-    cc, cflags = _make_vars()
-    os.makedirs(BUILD_DIR, exist_ok=True)
-    tmp = LIB + f".{os.getpid()}.tmp"
-    subprocess.run([cc, *cflags, "-shared", "-o", tmp, SRC, "-lm"], check=True, cwd=HERE)
-    os.replace(tmp, LIB)
 
 
 def lib():
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB) or os.path.getmtime(SRC) > os.path.getmtime(LIB):
-            build()
-        L = ct.CDLL(LIB)
+        L = checker_build.load("zv_oracle.c", "libzv_oracle.so")
         i64, D = ct.c_int64, ct.POINTER(ct.c_double)
         L.orc_zv.restype = ct.c_int
         L.orc_zv.argtypes = [ct.c_int, D, D, i64, i64, i64, D, D, ct.POINTER(ct.c_int32)]
