@@ -449,6 +449,59 @@ int mcmc_run_serialtempmc(mcmc_chains* const* targets, int32_t ntargets, int64_t
                           double* samples, int32_t* models, uint64_t* swap_bits, int32_t* final_at,
                           double* runtime_s);
 
+/* ---- slice sampling (src/samplers/slice_sample.jl:43-103) ----
+ * Neal's univariate-at-a-time slice sampler with stepping out and shrinkage, as the reference writes it, for nchains
+ * independent chains of one catalogue model: a function on the model's log-density, not an MCMCSampler -- no
+ * mcmc_sampler_cfg, no mcmc_chains.  Every logdist(...) of the reference is one full evaluation of the d-vector,
+ * bitwise what mcmc_model_eval returns for it.  Per iteration iter = iter_begin + 1 .. iter_begin + burnin + niter and
+ * coordinate dd = 0 .. d - 1 in order:
+ *   log_uprime = log(u0) + log_Px;  x_l = state[dd] - r w[dd];  x_r = state[dd] + (1 - r) w[dd]  (the product rounded,
+ *   then the sum);  step_out: while logdist(x_l) > log_uprime: x_l -= w[dd], likewise x_r += w[dd];  shrink:
+ *   xprime = u_k (x_r - x_l) + x_l (three roundings), log_Px = logdist(xprime), accepted iff log_Px > log_uprime (a NaN
+ *   is not), else x_r = xprime if xprime > state[dd], x_l = xprime if xprime < state[dd].
+ * After the sweep of iteration iter > iter_begin + burnin the state is row iter - iter_begin - burnin - 1 of samples.
+ * Draw k of the update (iter, dd) is the 52-bit uniform of words (w0, w1) (k even) or (w2, w3) (k odd) of the Philox
+ * block (global chain id, iter, (dd << 20) | (k >> 1), tag 9) under `seed`: k = 0 is u0, k = 1 is r, k >= 2 is shrink
+ * proposal k - 2.  So a run of a + b iterations is bitwise a run of a followed by one of b with iter_begin = a from the
+ * first run's final_x, and results do not depend on how chains are split over calls (chain_offset).
+ * Where the reference would loop without end or assert:
+ *   - a start whose log-density is not finite answers MCMC_E_INIT_OUT_OF_SUPPORT;
+ *   - one coordinate update may spend max_evals evaluations, stepping out and shrinking together.  A chain whose update
+ *     is not finished after that many, or whose xprime == state[dd] and still is not acceptable (slice_sample.jl:92),
+ *     stops: info[c] = the iteration, counted from iter_begin, 1-based (saturating at 2^31 - 1); final_x and final_lp
+ *     keep its last completed iteration's state; its rows of samples from that iteration on are NaN.  The other chains
+ *     are unaffected and the call answers MCMC_OK.  info[c] = 0 otherwise.  max_evals is a guard against unbounded
+ *     loops on a shared GPU, not a tuning knob: 3 .. 2^20, 0 -> 4096.
+ * Built for the separable and joint targets with d <= 32 (ISO_NORMAL_DOT, NORMAL_DSL, ABS_NORMAL_DSL, DIST_DSL,
+ * DIST_OBS, OU); the regression models and wider d answer MCMC_E_UNSUPPORTED.  A long run is split by the library into
+ * launches of at most 256 whole iterations; the split changes no result.
+ *   init_x   : [d][nchains] per-chain starts, or NULL -> model.init for every chain
+ *   widths   : host [d], finite and > 0 (else MCMC_E_INVALID_ARG), or NULL -> ones
+ *   samples  : [niter][d][nchains] (the mcmc_outputs layout: mcmc_stats_ess, mcmc_stats_describe and mcmc_stats_zv's
+ *              sample argument read it in place), or NULL
+ *   final_x  : [d][nchains], final_lp : [nchains], info : int32 [nchains]; any may be NULL
+ *   evals    : host, every logdist call of the run over all chains, the nchains initial ones included, or NULL
+ *   runtime_s, kernel_ms : host, wall time of the run and device time of its kernels, or NULL
+ * on_device != 0: init_x, samples, final_x, final_lp and info are device pointers on the model's GPU. */
+typedef struct {
+    int64_t niter;           /* iterations recorded (> 0)                                                */
+    int64_t burnin;          /* iterations run first without recording (>= 0)                            */
+    int64_t iter_begin;      /* iterations this chain has run before (>= 0): keys the draws             */
+    int32_t step_out;        /* 0: the widths are known to be large enough (slice_sample.jl:23-24)       */
+    int64_t max_evals;       /* evaluations one coordinate update may spend: 3 .. 2^20, 0 -> 4096        */
+} mcmc_slice_cfg;
+int mcmc_slice_validate(const mcmc_slice_cfg* cfg);
+int mcmc_run_slice(mcmc_model* model, const mcmc_slice_cfg* cfg, int64_t nchains, int64_t chain_offset, uint64_t seed,
+                   const double* init_x, const double* widths, int32_t on_device, double* samples, double* final_x,
+                   double* final_lp, int32_t* info, int64_t* evals, double* runtime_s, double* kernel_ms);
+/* The kernel instance mcmc_run_slice launches for (model kind, d, nchains), as rocprofv3 names it without the namespace
+ * ("lpc_slice<NB, Model>", "lpp_slice<NBL, Model>"), its block size and its grid; needs no GPU.  A combination that is
+ * not built answers MCMC_E_UNSUPPORTED.  name (cap bytes), threads and grid may be NULL. */
+int mcmc_slice_plan(int32_t model_kind, int64_t d, int64_t nchains, char* name, int64_t cap, int32_t* threads,
+                    int64_t* grid);
+/* the instance the calling thread's last mcmc_run_slice launched ("" before the first) */
+int mcmc_slice_last_kernel(char* buf, int64_t cap);
+
 /* ---- output analysis (src/stats/ess.jl:6-10, var.jl:7-117) ----
  * Effective sample size n * var_iid / var_vtype of every (parameter j, chain c) series of
  * samples [nkept][d][nchains] (the mcmc_outputs layout).  vtype: MCMC_VAR_IMSE (Geyer initial

@@ -119,6 +119,28 @@ struct LeapRec {
     int32_t* nl;
 };
 
+// One launch of the slice-sampling kernels (kernels/slice_impl.hpp): whole iterations iter_first .. iter_first +
+// niters - 1 of every chain.  Their own block: StepArgs is every other kernel's kernarg.
+struct SliceArgs {
+    int64_t C;                  // local chains
+    int64_t ld;                 // leading dimension of x (>= C, multiple of 64)
+    int32_t d;
+    uint32_t chain0;            // global id of local chain 0
+    uint32_t key0, key1;        // seed
+    int64_t iter_first;         // global iteration index of the launch's first iteration (1-based)
+    int32_t niters;             // iterations in this launch
+    int64_t iter_begin;         // the call's iter_begin: info is the iteration counted from it
+    int64_t keep_after;         // iter_begin + burnin: iteration iter > keep_after is row iter - keep_after - 1
+    int32_t step_out;
+    int32_t max_evals;          // evaluations one coordinate update may spend
+    const double* widths;       // [d]
+    double* x;                  // [d][ld] the last completed state
+    double* lp;                 // [ld]    its log-density
+    int32_t* info;              // [ld]    0, or the iteration at which the chain stopped
+    double* samples;            // [niter][d][C] (NULL: not stored)
+    unsigned long long* n_evals;   // running count of evaluations over all chains
+};
+
 __host__ __device__ inline bool kept_index(int64_t i_loc, int64_t burnin, int64_t thinning, int64_t len,
                                            int64_t* kk) {
     if (i_loc <= burnin || i_loc > len) return false;

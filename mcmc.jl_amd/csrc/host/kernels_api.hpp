@@ -13,6 +13,11 @@ struct KernelArgs {
     ModelArgs m;
     ChainState st;
 };
+// the slice-sampling kernels' block (slice.hip)
+struct SliceKernelArgs {
+    ModelArgs m;
+    SliceArgs s;
+};
 }  // namespace mcmc
 
 // The step kernel a launch function dispatched, as "family<template arguments>" (the instance name rocprofv3
@@ -34,6 +39,10 @@ int mcmc_lpc_max_d();
 hipError_t mcmc_launch_nuts(const mcmc::KernelArgs& a, int init, hipStream_t st);
 int mcmc_nuts_max_d();
 int mcmc_nuts_max_doublings();
+// slice sampling (slice.hip), lane-per-chain state [d][ld], d <= mcmc_slice_max_d(): a.s.niters whole iterations of
+// every chain; the launched instance is noted like a step kernel's
+hipError_t mcmc_launch_slice(const mcmc::SliceKernelArgs& a, hipStream_t st);
+int mcmc_slice_max_d();
 // wave- and block-per-chain kernels (32 < d <= mcmc_wpc_max_d() = 16384; RAM: d <= mcmc_wpc_ram_max_d() = 1024),
 // state [C][ld] (ld = row stride, multiple of 4)
 hipError_t mcmc_launch_wpc_step(const mcmc::KernelArgs& a, hipStream_t st);

@@ -1,6 +1,6 @@
 // launch_plan.hpp -- which kernel instance of the separable and joint targets a launch runs, with what grid and block,
 // and the name it reports: the instance rule, stated once.  Plain C++: no HIP runtime is needed, so
-// tests/launch_plan_check.cpp walks it on the CPU.  lpc_impl.hpp, wpc_impl.hpp, nuts_impl.hpp and wpc_ram.hip launch
+// tests/launch_plan_check.cpp walks it on the CPU.  lpc_impl.hpp, wpc_impl.hpp, nuts_impl.hpp, slice_impl.hpp and wpc_ram.hip launch
 // what the plan names; the kernels' __launch_bounds__ read the block sizes below.  A host compiler that includes it
 // defines __host__ and __device__ to nothing first (common.hpp marks its argument blocks with them), as for tables.hpp.
 #pragma once
@@ -19,6 +19,7 @@ constexpr int kBlockMaxD = 16384;     // bpc: W waves per chain; the state layou
 constexpr int kRamHalfMaxD = 256;     // wpc_ram2: two chains per wave, G slot groups of 128 coordinates
 constexpr int kRamMaxD = 1024;        // wpc_ram
 constexpr int kNutsMaxD = kPairMaxD;
+constexpr int kSliceMaxD = kPairMaxD;
 constexpr int kLaMaxChains = 64;      // RWM on C <= 64 chains of d <= 32: lpc_rwm_la, one block
 constexpr int kSpecMaxD = 4;          // ... and on one chain of d <= 4: lpc_rwm_spec<d>
 constexpr int kPlanBlock = 256;       // samplers.hpp kBlock: every kernel without a size of its own
@@ -69,9 +70,10 @@ constexpr bool plan_same_name(const char* a, const char* b) {
 // A kernel family is a mapping and a body: <map>_<body>, e.g. lpp_rwm, wpc_ram2, lpc_nuts_init
 enum Mapping : int32_t { MAP_LPC, MAP_LPP, MAP_WPC, MAP_BPC };
 enum Body : int32_t {
-    B_RWM, B_RWM_LA, B_RWM_SPEC, B_MALA, B_HMC, B_RAM, B_RAM2, B_NUTS, B_NUTS_INIT, B_EVAL, B_HMC_REC
+    B_RWM, B_RWM_LA, B_RWM_SPEC, B_MALA, B_HMC, B_RAM, B_RAM2, B_NUTS, B_NUTS_INIT, B_EVAL, B_HMC_REC, B_SLICE
 };
-enum PlanOp : int32_t { OP_STEP, OP_EVAL, OP_RECORD, OP_NUTS_INIT };
+// OP_SLICE: the slice sampler (slice_impl.hpp), a function on a model and no sampler kind: `sampler` is not read
+enum PlanOp : int32_t { OP_STEP, OP_EVAL, OP_RECORD, OP_NUTS_INIT, OP_SLICE };
 
 struct KernelInstance {
     Mapping map;
@@ -109,6 +111,10 @@ inline LaunchPlan launch_plan(int32_t model, int32_t sampler, int d, int64_t C, 
         if (nb > pm.nuts_max_nb) return p;                           // at most 8: d <= kNutsMaxD
         const Body body = op == OP_STEP ? B_NUTS : B_NUTS_INIT;
         k = lane ? inst(MAP_LPC, body, nb, kPlanBlock) : inst(MAP_LPP, body, (nb + 1) / 2, kPlanBlock);
+    } else if (op == OP_SLICE) {
+        // d <= kSliceMaxD; the joint models at their catalogue sizes, like NUTS (nuts_max_nb)
+        if (!pair || nb > pm.nuts_max_nb) return p;
+        k = lane ? inst(MAP_LPC, B_SLICE, nb, kPlanBlock) : inst(MAP_LPP, B_SLICE, (nb + 1) / 2, kPlanBlock);
     } else if (op == OP_STEP && sampler == SK_RAM) {
         if (!pm.ram || d > kRamMaxD) return p;
         if (pair) k = inst(MAP_LPC, B_RAM, nb, kPlanBlock);
@@ -151,7 +157,7 @@ inline LaunchPlan launch_plan(int32_t model, int32_t sampler, int d, int64_t C, 
 inline int plan_kernel_name(char* buf, size_t size, const KernelInstance& k, const char* model) {
     static const char* const maps[] = {"lpc", "lpp", "wpc", "bpc"};
     static const char* const bodies[] = {"rwm", "rwm_la", "rwm_spec", "mala", "hmc", "ram", "ram2", "nuts", "nuts_init",
-                                         "eval", "hmc_rec"};
+                                         "eval", "hmc_rec", "slice"};
     const bool has_f = (k.body == B_RWM || k.body == B_MALA || k.body == B_HMC) && k.map != MAP_BPC;
     const bool has_us = k.body == B_RWM_LA || k.body == B_RWM_SPEC || (k.body == B_RWM && k.map <= MAP_LPP);
     const bool has_da = k.body == B_HMC || k.body == B_HMC_REC;

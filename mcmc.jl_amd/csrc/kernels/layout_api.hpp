@@ -23,6 +23,9 @@ UnitFn lpc_ram_iso, lpc_ram_normal, lpc_ram_absnormal, lpc_ram_dist, lpc_ram_ou;
 UnitFn wpc_iso, wpc_normal, wpc_absnormal, wpc_dist;
 UnitFn wpc_ram_iso, wpc_ram_normal, wpc_ram_absnormal, wpc_ram_dist;
 UnitFn nuts_iso, nuts_normal, nuts_absnormal, nuts_dist, nuts_distobs, nuts_ou;
+// the slice units (slice_<model>.hip) export their one launcher; slice.hip's table holds them
+using SliceFn = hipError_t(const SliceKernelArgs& a, const LaunchPlan& p, hipStream_t st);
+SliceFn slice_iso, slice_normal, slice_absnormal, slice_dist, slice_distobs, slice_ou;
 
 // a mapping's table: one row per model kind; a null unit, like a null entry, is refused with hipErrorInvalidValue
 struct UnitRow {

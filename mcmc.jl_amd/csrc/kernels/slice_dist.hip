@@ -1,0 +1,3 @@
+// slice-sampling kernels of one model (slice_impl.hpp); separate units compile in parallel
+#include "slice_impl.hpp"
+SLICE_UNIT(dist, DistDSL, MK_DIST)

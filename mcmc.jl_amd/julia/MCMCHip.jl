@@ -155,6 +155,41 @@ function run_serialtempmc(targets::Vector{Ptr{Cvoid}}, d, nwalkers; steps = 1, b
     smp, mod .+ Int32(1), swap, final .+ Int32(1), rt[]
 end
 
+# slice_sample (slice_sample.jl:43-112) for nchains independent chains of a catalogue model (d <= 32): a function on
+# the model's log-density, no sampler and no runner.  initial: a d-vector (every chain starts there) or a (nchains, d)
+# matrix of per-chain starts.  Returns the history (nchains, d, niter), the final states (nchains, d), info (nchains;
+# nonzero: the iteration at which the chain spent max_evals evaluations on one coordinate update and stopped) and the
+# number of log-density evaluations.
+struct SliceCfg
+    niter::Int64
+    burnin::Int64
+    iter_begin::Int64
+    step_out::Int32
+    max_evals::Int64
+end
+slice_validate(cfg::SliceCfg) = check(ccall((:mcmc_slice_validate, lib), Cint, (Ref{SliceCfg},), cfg))
+
+function slice_sample(model, initial, niter; widths = nothing, step_out = true, burnin = 0, nchains = 1, seed = 1,
+                      chain_offset = 0, iter_begin = 0, max_evals = 0)
+    cfg = SliceCfg(niter, burnin, iter_begin, step_out ? 1 : 0, max_evals)
+    slice_validate(cfg)
+    d = ndims(initial) == 2 ? size(initial, 2) : length(initial)
+    x0 = ndims(initial) == 2 ? convert(Matrix{Float64}, initial) : repeat(reshape(convert(Vector{Float64}, vec([initial;])), 1, d), nchains, 1)
+    @assert size(x0) == (nchains, d)
+    wv = widths === nothing ? Float64[] : convert(Vector{Float64}, widths)
+    @assert widths === nothing || length(wv) == d                                  # slice_sample.jl:49
+    w = widths === nothing ? Ptr{Float64}(C_NULL) : pointer(wv)
+    smp = Array{Float64}(undef, nchains, d, niter)
+    fx = Array{Float64}(undef, nchains, d)
+    info = zeros(Int32, nchains)
+    evals = Ref{Int64}(0)
+    GC.@preserve x0 wv check(ccall((:mcmc_run_slice, lib), Cint,
+        (Ptr{Cvoid}, Ref{SliceCfg}, Int64, Int64, UInt64, Ptr{Float64}, Ptr{Float64}, Int32, Ptr{Float64}, Ptr{Float64},
+         Ptr{Float64}, Ptr{Int32}, Ref{Int64}, Ptr{Float64}, Ptr{Float64}),
+        model, cfg, nchains, chain_offset, seed, x0, w, 0, smp, fx, C_NULL, info, evals, C_NULL, C_NULL))
+    smp, fx, info, evals[]
+end
+
 # linearZv / quadraticZv (zv.jl:8-68) of every chain: samples and gradients of size (C, d, nkept) -> the ZV chains
 # (C, d, nkept), the coefficients (C, d, k) and info (C; nonzero: the chain's Gram matrix is not positive definite)
 function stats_zv(ctx, smp::Array{Float64,3}, grd::Array{Float64,3}; order = 1)

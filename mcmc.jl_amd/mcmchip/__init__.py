@@ -13,6 +13,7 @@ from .api import (  # noqa: F401
 )
 from .seqmc import SeqMC, SeqMCChain, run_seqmc, resume_seqmc  # noqa: F401
 from .serialtemp import SerialTempMC, run_serialtempmc, resume_serialtempmc  # noqa: F401
+from .slice import slice_sample, slice_plan, slice_last_kernel, SliceChain  # noqa: F401
 from . import stats  # noqa: F401
 from .stats import acceptance, mean, var, ess, actime, mcvar_iid, mcvar_bm, mcvar_imse, mcvar_ipse  # noqa: F401
 from .stats import linear_zv, quadratic_zv, zv_device  # noqa: F401

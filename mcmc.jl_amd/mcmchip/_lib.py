@@ -76,7 +76,8 @@ EXPORTED_SYMBOLS = (
     "mcmc_group_chains_set_steps_per_launch", "mcmc_group_chains_block", "mcmc_group_run_serialmc",
     "mcmc_group_last_pin_s",
     "mcmc_debug_group_inject_failure",
-    "mcmc_seqmc_validate", "mcmc_run_seqmc", "mcmc_serialtempmc_validate", "mcmc_run_serialtempmc", "mcmc_stats_ess", "mcmc_stats_describe", "mcmc_stats_zv",
+    "mcmc_seqmc_validate", "mcmc_run_seqmc", "mcmc_serialtempmc_validate", "mcmc_run_serialtempmc",
+    "mcmc_slice_validate", "mcmc_run_slice", "mcmc_slice_plan", "mcmc_slice_last_kernel", "mcmc_stats_ess", "mcmc_stats_describe", "mcmc_stats_zv",
     "mcmc_debug_detmath", "mcmc_debug_philox",
     "mcmc_debug_mfma_f64", "mcmc_debug_chains_order",
 )
@@ -114,6 +115,11 @@ class Outputs(ct.Structure):
         ("final_x", ct.c_void_p), ("final_lp", ct.c_void_p), ("on_device", ct.c_int32),
         ("runtime_s", ct.c_double), ("kernel_ms", ct.c_double), ("nkept", ct.c_int64),
     ]
+
+
+class SliceCfg(ct.Structure):
+    _fields_ = [("niter", ct.c_int64), ("burnin", ct.c_int64), ("iter_begin", ct.c_int64), ("step_out", ct.c_int32),
+                ("max_evals", ct.c_int64)]
 
 
 class MCMCError(RuntimeError):
@@ -207,6 +213,12 @@ def load() -> ct.CDLL:
         "mcmc_run_serialtempmc": (ct.c_int, [ct.POINTER(ct.c_void_p), i32, i64, ct.c_void_p, ct.c_void_p, u64, i32,
                                              ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p,
                                              ct.POINTER(ct.c_double)]),
+        "mcmc_slice_validate": (ct.c_int, [ct.POINTER(SliceCfg)]),
+        "mcmc_run_slice": (ct.c_int, [P, ct.POINTER(SliceCfg), i64, i64, u64, ct.c_void_p, ct.c_void_p, i32,
+                                      ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.c_void_p, ct.POINTER(i64),
+                                      ct.POINTER(ct.c_double), ct.POINTER(ct.c_double)]),
+        "mcmc_slice_plan": (ct.c_int, [i32, i64, i64, ct.c_char_p, i64, ct.POINTER(i32), ct.POINTER(i64)]),
+        "mcmc_slice_last_kernel": (ct.c_int, [ct.c_char_p, i64]),
         "mcmc_stats_ess": (ct.c_int, [P, ct.c_void_p, i64, i64, i64, i32, i64, i64, i32, ct.c_void_p,
                                       ct.c_void_p]),
         "mcmc_stats_describe": (ct.c_int, [P, ct.c_void_p, i64, i64, i64, i64, i32, ct.c_void_p, ct.c_void_p, i32,
