@@ -138,8 +138,9 @@ def test_python_surface():
         stats.zv_device((np.zeros((5, 1, 1)), np.zeros((5, 1, 1))), order=3)
 
 
-# (order, d): the small widths, where a stuck chain's rounding residue most often factorises "successfully"
-STUCK = ((1, 1), (1, 2), (1, 3), (2, 1), (2, 2), (1, 8))
+# (order, d): the small widths, where a stuck chain's rounding residue most often factorises "successfully", then the
+# largest width of the one-tile quadratic instance and one width for each kernel instance the small ones do not select
+STUCK = ((1, 1), (1, 2), (1, 3), (2, 1), (2, 2), (1, 8), (1, 17), (2, 4), (2, 5), (2, 7))
 STUCK_VALUES = (0.0, 1.0, -1e-3, 0.1, 57.3, 1e4 / 3, 1e-300)
 
 

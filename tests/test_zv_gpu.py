@@ -2,6 +2,15 @@
 bit for bit on zv, coef and info: the MFMA row-tile edge d = 16 | 17, ragged chain tiles, the minimum nkept = k + 1,
 a remainder of the MFMA k = 4 and an odd staging tail, a singular chain inside a tile, the device-pointer path, a real
 run, and the refusals.
+
+The tables of tests/zv_cases.py (their premises asserted with the checker alone in tests/test_zv_cases_cpu.py) add:
+every one of the five instances k_zv<F, NTK, NTD> at its smallest and largest width -- <ZvQuadratic, 2, 1> (d = 5, 6)
+among them -- with nkept at, one below and one above the multiples of the 16-step staging block; chains whose
+factorisation fails inside zv_solve at the pivot of the first, a middle and the last gradient coordinate (an exact zero,
+NaN, +inf, an overflowing Gram diagonal), placed before, after and beside a healthy chain of the same solve block, at a tile's first chain and in a
+ragged tile, with every other chain equal to a run of the unmodified inputs; a duplicated coordinate, whose pivot is
+rounding residue; chains whose only moves lie on the staging block's boundaries; a grid of a thousand tiles; the
+device-pointer path and a real quadratic run on the two-tile instance.
 """
 import ctypes as ct
 import functools
@@ -10,9 +19,11 @@ import numpy as np
 import pytest
 
 import mcmchip as mc
+import zv_cases as zc
 import zv_ref
 from mcmchip import _lib, stats
-from test_zv import STUCK, normal_hmc, stuck_inputs, synthetic
+from test_zv import STUCK, normal_hmc, stuck_inputs
+from test_zv_cases_cpu import moves_of, normal_hmc_d5
 
 # a pairwise-sparse subset of d x C x nkept (nkept: 0 -> d + 1, 1 -> d + 2, else itself): every d meets every kind of
 # nkept, every C every d class
@@ -30,14 +41,7 @@ def _n(order, d, nk):
     return k + 1 if nk == 0 else k + 2 if nk == 1 else nk
 
 
-@functools.lru_cache(maxsize=None)
-def case(order, d, C, n):
-    """inputs and the checker's answer, computed once and left unchanged"""
-    x, g = synthetic(d, C, n, seed=100 * order + d)
-    out = zv_ref.zv(order, x, g)
-    for v in (x, g) + out:
-        v.setflags(write=False)
-    return x, g, out
+case = zc.case          # (order, d, C, n) -> inputs (seed 100 order + d) and the checker's answer, computed once
 
 
 def device_zv(order, x, g, coef=True, info=True):
@@ -91,8 +95,8 @@ def test_singular_chain_leaves_its_tile_alone(gpu):
 @pytest.mark.gpu
 @pytest.mark.parametrize("order,d", STUCK)
 def test_stuck_chains_are_marked_whatever_their_value(gpu, order, d):
-    """chains that never moved (several constants) and chains with too few moves, at the small widths: info, NaN and
-    the healthy neighbours as the checker has them"""
+    """chains that never moved (several constants) and chains with too few moves, at the small widths and at one width of
+    every kernel instance: info, NaN and the healthy neighbours as the checker has them"""
     x, g, want = stuck_inputs(order, d)
     got = device_zv(order, x, g)
     for c, w in enumerate(want):
@@ -158,3 +162,105 @@ def test_refusals_and_argument_errors(gpu):
         stats.zv_device(ch)
     with pytest.raises(ValueError, match="gradients"):
         stats.linear_zv(ch)
+
+
+# ---- the tables of zv_cases.py: every instance, the staging block's edges, chains that fail inside zv_solve
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("order,d,C,n", zc.PARITY)
+def test_every_instance_matches_checker(gpu, order, d, C, n):
+    x, g, want = zc.case(order, d, C, n)
+    assert_same(device_zv(order, x, g), want)
+    assert not want[2].any()
+
+
+@functools.lru_cache(maxsize=None)
+def device_healthy(order, d):
+    """the device's answer for the unmodified inputs of the PIVOT / NONFINITE / DUPLICATE cases, computed once"""
+    x, g, want = zc.healthy(order, d)
+    got = device_zv(order, x, g)
+    assert_same(got, want, "unmodified inputs")
+    for v in got:
+        v.setflags(write=False)
+    return got
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("order,d,j,v,chains", [(o, d, j, None, p) for o, d, j, p in zc.PIVOT] + list(zc.NONFINITE))
+def test_failing_pivot_marks_its_chain_only(gpu, order, d, j, v, chains):
+    """pivot j + 1 of a chain with n - 1 moves is an exact zero (v None: PIVOT) or not finite (NONFINITE: one gradient
+    entry NaN, +inf or 1e200, the last overflowing the Gram diagonal): zv_solve's failing return, which leaves a partly
+    factorised block to the next chain of the solve batch.  NaN out, info = j + 1, every other chain as if nothing
+    had failed."""
+    x, g = zc.pivot_inputs(order, d, j, chains) if v is None else zc.nonfinite_inputs(order, d, j, v, chains)
+    got = device_zv(order, x, g)
+    z, a, info = got
+    bad = list(chains)
+    assert (info[bad] == j + 1).all() and not np.delete(info, bad).any(), info
+    assert np.isnan(z[:, :, bad]).all() and np.isnan(a[:, :, bad]).all()
+    assert_same(got, zv_ref.zv(order, x, g), "against the checker")
+    z0, a0, _ = device_healthy(order, d)
+    assert np.array_equal(bits(np.delete(z, bad, axis=2)), bits(np.delete(z0, bad, axis=2)))
+    assert np.array_equal(bits(np.delete(a, bad, axis=2)), bits(np.delete(a0, bad, axis=2)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("order,d", zc.DUPLICATE)
+def test_duplicate_coordinate_factorises_like_the_checker(gpu, order, d):
+    """an exactly singular G whose second pivot is rounding residue: any change in the order of operations shows"""
+    x, g = zc.duplicate_inputs(order, d)
+    got = device_zv(order, x, g)
+    assert_same(got, zv_ref.zv(order, x, g))
+    z0, a0, _ = device_healthy(order, d)
+    c = zc.DUPLICATE_CHAIN
+    assert np.array_equal(bits(np.delete(got[0], c, axis=2)), bits(np.delete(z0, c, axis=2)))
+    assert np.array_equal(bits(np.delete(got[1], c, axis=2)), bits(np.delete(a0, c, axis=2)))
+
+
+@pytest.mark.gpu
+def test_moves_on_staging_block_boundaries(gpu):
+    x, g = zc.boundary_inputs()
+    got = device_zv(zc.BOUNDARY_ORDER, x, g)
+    for c in range(zc.BOUNDARY_C):
+        want = zc.BOUNDARY_MOVES[c][1] if c in zc.BOUNDARY_MOVES else 0
+        if want is not None:
+            assert got[2][c] == want, (c, got[2][c], want)
+    assert_same(got, zv_ref.zv(zc.BOUNDARY_ORDER, x, g))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("order,d,C,n", zc.MANY_TILES)
+def test_many_tiles(gpu, order, d, C, n):
+    x, g, want = zc.case(order, d, C, n)
+    assert_same(device_zv(order, x, g), want)
+
+
+@pytest.mark.gpu
+def test_device_pointers_and_null_outputs_two_tile_instance(gpu):
+    import torch
+    x, g, want = zc.case(2, 6, 17, 33)
+    assert zc.instance_of(2, 6) == (2, 2, 1)
+    dev = torch.device("cuda", 0)
+    tx, tg = torch.from_numpy(x.copy()).to(dev), torch.from_numpy(g.copy()).to(dev)
+    z, a, i = stats.zv_device((tx, tg), order=2, return_coef=True, return_info=True)
+    assert z.device == tx.device and z.shape == tx.shape and a.shape == (27, 6, 17) and i.shape == (17,)
+    assert_same((z.cpu().numpy(), a.cpu().numpy(), i.cpu().numpy()), want, "device tensors")
+    only = stats.zv_device((tx, tg), order=2)                          # coef = NULL, info = NULL
+    assert np.array_equal(bits(only.cpu().numpy()), bits(want[0]))
+    assert np.array_equal(bits(tx.cpu().numpy()), bits(x)) and np.array_equal(bits(tg.cpu().numpy()), bits(g))
+
+
+@pytest.mark.gpu
+def test_end_to_end_quadratic_on_the_two_tile_instance(gpu):
+    m = mc.model(mc.NormalDSL(1, 2), v=np.ones(5), gradient=True)
+    ch = mc.run((m * mc.HMC() * mc.SerialMC(steps=60)).batch(70, seed=1))
+    z, a, info = stats.zv_device(ch, order=2, return_coef=True, return_info=True)
+    want = zv_ref.zv(2, ch._samples, ch._gradients)
+    assert z.shape == ch.samples.shape == (70, 60, 5) and a.shape == (70, 20, 5)
+    assert_same((z.transpose(1, 2, 0), a.transpose(1, 2, 0), info), want)
+    s, g = normal_hmc_d5()                                             # the CPU oracle's run says what info must be
+    assert np.array_equal(bits(ch._samples), bits(s)) and np.array_equal(bits(ch._gradients), bits(g))
+    moves = moves_of(s, g)
+    few = moves < 20
+    assert np.array_equal(info[few], moves[few] + 1)
